@@ -10,6 +10,7 @@ R=$PWD
 export TMPDIR=/tmp
 T=${T:-r05}
 STEPS=${STEPS:-"bench prof pmc"}   # also: tests segbench configs
+BENCH_ARGS=${BENCH_ARGS:---full}   # the bench step's line carries every side measurement (bench.py --full)
 mkdir -p gpurun_out
 for step in $STEPS; do
   case $step in
@@ -52,7 +53,7 @@ for step in $STEPS; do
       # world-size-2 rehearsal of the bench on the box's one GPU (gloo: RCCL cannot put two ranks on
       # one device), timed at the chain's steady state like the N = 1 line
       RVM_DIST_BACKEND=gloo timeout -k 10 600 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-        --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 20 --warmup 3 --ess-iters 2000 --no-cpu \
+        --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 20 --warmup 3 --ess-iters 2000 --no-cpu \
         > gpurun_out/${T}_bench_n2_gloo.json 2> gpurun_out/${T}_bench_n2_gloo.err \
         || { tail -30 gpurun_out/${T}_bench_n2_gloo.err; exit 1; }
       head -c 600 gpurun_out/${T}_bench_n2_gloo.json; echo ;;
@@ -68,7 +69,7 @@ for step in $STEPS; do
       mkdir -p gpurun_out/${T}_prof_steady
       cd /tmp
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$R/gpurun_out/${T}_prof_steady" -o run --output-format csv -- \
-        python3 "$R/bench.py" --steps 20 --warmup 3 --ball-steps 0 --burn-in 3000 --ess-iters 0 --kernel-iters 64 \
+        python3 "$R/bench.py" --full --steps 20 --warmup 3 --ball-steps 0 --burn-in 3000 --ess-iters 0 --kernel-iters 64 \
         --no-cpu --no-fixed-step-ref > "$R/gpurun_out/${T}_bench_under_rocprof.json" 2> "$R/gpurun_out/${T}_bench_under_rocprof.err"
       cd "$R"
       tr=$(find gpurun_out/${T}_prof_steady -name "*kernel_trace.csv" | head -1)

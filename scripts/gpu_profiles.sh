@@ -19,8 +19,8 @@ if [ "${SKIP_PMC:-0}" != 1 ]; then
   grep -E "hbm_bytes_per_launch\"|fp64_flops_per_eval|kernel_signature" gpurun_out/pmc/summary.txt
   cp gpurun_out/pmc/pmc_latest.json profiles/pmc_latest.json
 fi
-timeout -k 10 300 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err || { tail -30 gpurun_out/bench.err; exit 1; }
-cat gpurun_out/bench.json
+# (the bench step of scripts/gpu_evidence.sh: bench.py --full, its line saved as bench_bench.json beside the other outputs)
+T=bench STEPS=bench bash scripts/gpu_evidence.sh
 # the N > 1 flow of bench.py (2 ranks on this one GPU over gloo: correctness, not scaling)
 bash scripts/gpu_rehearse_dist.sh > /dev/null
 cd /tmp
