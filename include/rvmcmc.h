@@ -260,6 +260,44 @@ int rvm_stretch_iteration_end(int32_t n_params, int32_t n_loc, int64_t s0_begin,
                               uint64_t iteration, int32_t* accepted1, double* lnp_new_out, int32_t* status_new_out,
                               void* stream);
 
+/* ---- parallel tempering of the stretch-move ensemble ----------------------------------------------
+ * n_temps ensembles of W = 2 n_half walkers at inverse temperatures betas[0] > betas[1] > ... > 0
+ * (a device array [n_temps]; temperature 0 is the coldest, betas[0] = 1 samples the posterior; the
+ * caller validates the values).  Each half h is SoA [n_params][n_temps * n_half], column
+ * i = t * n_half + k, with the UNtempered log-probabilities lnp [n_temps * n_half].  The Philox item
+ * of walker k of half h at temperature t is g = t * W + h * n_half + k (at n_temps = 1 the global
+ * walker index of rvm_stretch_propose / rvm_stretch_accept, whose bits these entries then give).
+ * One iteration: propose, rvm_logl_batch of the n_temps * n_half proposals and accept for half 0,
+ * the same for half 1, then (every few iterations) the exchange sweep.
+ * Argument errors (n_params, n_temps or n_half < 1; n_temps * n_half beyond int32; half > 1; a <= 1;
+ * a null required pointer) return < 0 before any HIP call.
+ *
+ * propose: as rvm_stretch_propose with x this half and c the OTHER half (both [n_params][n_temps *
+ *   n_half]): walker (t, k) draws its partner j = floor(u2 * n_half) among its own temperature's
+ *   walkers of c, column t * n_half + j.  Stream RNG_STRETCH_PROPOSE | half << 8, item g.  Writes
+ *   q_out [n_params][n_temps * n_half], z_out [n_temps * n_half].  draws layout: [2][n_temps * n_half]
+ *   (u1, u2).
+ * accept: lnpdiff = (n_params-1) ln z + betas[t] * lnp_new - betas[t] * lnp_old > ln(u3)  (evaluated
+ *   left to right) -> x <- q, lnp <- lnp_new; a -inf lnp_new is rejected, lnp_old must be finite.
+ *   u3: stream RNG_STRETCH_ACCEPT | half << 8, item g.  accepted (nullable): int32 counters
+ *   [n_temps * n_half] (+= 1).  draws layout: [n_temps * n_half] (u3).
+ * swap: the sweep over the pairs p = n_temps-2 .. 0 (hottest pair first); pair p exchanges walker
+ *   w = h * n_half + k of temperature p with walker w of temperature p + 1 when
+ *   (betas[p] - betas[p+1]) * (lnp[p+1][w] - lnp[p][w]) > ln(u): their position columns and lnp
+ *   values trade places (x0, lnp0: half 0; x1, lnp1: half 1; in place) and swapped[p][w] += 1
+ *   (int32 [n_temps-1][W]).  u: the first uniform of stream 7 (RNG_PT_SWAP), item p * W + w.
+ *   draws layout: [n_temps-1][W].  One thread carries walker index w through the whole sweep: no
+ *   atomics, deterministic.  n_temps = 1 returns 0 without a launch (the array arguments are not read). */
+int rvm_pt_stretch_propose(int32_t n_params, int32_t n_temps, int32_t n_half, const double* x, const double* c,
+                           double a, uint64_t seed, uint64_t iteration, uint32_t half, const double* draws,
+                           double* q_out, double* z_out, void* stream);
+int rvm_pt_stretch_accept(int32_t n_params, int32_t n_temps, int32_t n_half, const double* betas, double* x,
+                          double* lnp, const double* q, const double* lnp_new, const double* z, uint64_t seed,
+                          uint64_t iteration, uint32_t half, const double* draws, int32_t* accepted, void* stream);
+int rvm_pt_swap(int32_t n_params, int32_t n_temps, int32_t n_half, const double* betas, double* x0, double* x1,
+                double* lnp0, double* lnp1, uint64_t seed, uint64_t iteration, const double* draws,
+                int32_t* swapped, void* stream);
+
 /* Gaussian random-walk Metropolis-Hastings (mcmc.py:89-121), n_chains independent chains:
  * propose: q = x + step_size * scales[p] * N(0,1)        draws layout: [n_params][n_chains]
  * accept : exp(lnp_new - lnp_old) > u -> x <- q, lnp <- lnp_new   draws layout: [n_chains] */

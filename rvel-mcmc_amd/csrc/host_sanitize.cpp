@@ -58,6 +58,22 @@ int main() {
            "half_step null plan");
     expect(rvm_stretch_propose(0, 1, 0, nullptr, 1, nullptr, 2.0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr) < 0,
            "propose bad");
+    // parallel tempering: every refusal comes before any HIP call (the int32 bound in 64-bit arithmetic)
+    double d1 = 0.5;
+    int32_t i1 = 0;
+    expect(rvm_pt_stretch_propose(10, 0, 1, &d1, &d1, 2.0, 0, 0, 0, nullptr, &d1, &d1, nullptr) < 0, "pt n_temps 0");
+    expect(rvm_pt_stretch_propose(10, 2, 1, &d1, &d1, 1.0, 0, 0, 0, nullptr, &d1, &d1, nullptr) < 0, "pt a = 1");
+    expect(rvm_pt_stretch_propose(10, 1 << 16, 1 << 16, &d1, &d1, 2.0, 0, 0, 0, nullptr, &d1, &d1, nullptr) < 0,
+           "pt int32 overflow");
+    expect(rvm_pt_stretch_accept(10, 2, 1, nullptr, &d1, &d1, &d1, &d1, &d1, 0, 0, 0, nullptr, &i1, nullptr) < 0,
+           "pt null betas");
+    expect(rvm_pt_stretch_accept(10, 2, 1, &d1, &d1, &d1, &d1, &d1, &d1, 0, 0, 2, nullptr, &i1, nullptr) < 0,
+           "pt half 2");
+    expect(rvm_pt_swap(10, 2, 0, &d1, &d1, &d1, &d1, &d1, 0, 0, nullptr, &i1, nullptr) < 0, "pt n_half 0");
+    expect(rvm_pt_swap(10, 1 << 15, 1 << 15, &d1, &d1, &d1, &d1, &d1, 0, 0, nullptr, &i1, nullptr) < 0,
+           "pt swap int32 overflow");
+    expect(rvm_pt_swap(10, 1, 4, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr) == 0,
+           "pt swap of one temperature");
     expect(rvm_mh_accept(0, 1, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr) < 0, "mh bad");
     expect(rvm_fd_params(10, 1, nullptr, 1e-6, nullptr, nullptr, nullptr) < 0, "fd bad");
     const int32_t rows[2] = {0, 0};

@@ -46,6 +46,15 @@ hipError_t launch_mh_propose(int P, int n, int64_t b, const double* x, const dou
 hipError_t launch_mh_accept(int P, int n, int64_t b, double* x, double* lnp, const double* q, const double* lnp_new,
                             uint64_t seed, uint64_t it, const double* draws, int32_t* acc, hipStream_t st);
 hipError_t launch_stretch_iteration_end(const IterEndArgs& g, hipStream_t st);
+hipError_t launch_pt_stretch_propose(int P, int T, int Wh, const double* x, const double* c, double a, uint64_t seed,
+                                     uint64_t it, uint32_t half, const double* draws, double* q, double* z,
+                                     hipStream_t st);
+hipError_t launch_pt_stretch_accept(int P, int T, int Wh, const double* betas, double* x, double* lnp,
+                                    const double* q, const double* lnp_new, const double* z, uint64_t seed,
+                                    uint64_t it, uint32_t half, const double* draws, int32_t* acc, hipStream_t st);
+hipError_t launch_pt_swap(int P, int T, int Wh, const double* betas, double* x0, double* x1, double* lnp0,
+                          double* lnp1, uint64_t seed, uint64_t it, const double* draws, int32_t* swapped,
+                          hipStream_t st);
 hipError_t launch_fd_params(int P, int n, const double* x, double rel, const double* fl, double* out, hipStream_t st);
 hipError_t launch_smala_derive(int P, int C, int E, const double* x, double rel, const double* fl,
                                const double* lp_st, const int32_t* st_st, const double* rv, const double* w,
@@ -909,6 +918,55 @@ int rvm_stretch_accept(int32_t n_params, int32_t n_s0, int64_t s0_begin, double*
     hipError_t e = rvm::launch_stretch_accept(n_params, n_s0, s0_begin, x, lnp, q, lnp_new, z, seed, iteration, half,
                                               draws, accepted, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "rvm_stretch_accept");
+}
+
+// the scalar arguments the three parallel-tempering entry points share (null on success); `cols` =
+// columns per temperature the launch indexes with int32 (n_half, or 2 n_half for the exchange)
+static const char* pt_bad_shape(int32_t n_params, int32_t n_temps, int32_t n_half, int64_t cols) {
+    if (n_params < 1) return "n_params must be >= 1";
+    if (n_temps < 1) return "n_temps must be >= 1";
+    if (n_half < 1) return "n_half must be >= 1";
+    if ((int64_t)n_temps * cols > (int64_t)INT32_MAX) return "n_temps * n_half overflows int32";
+    return nullptr;
+}
+
+int rvm_pt_stretch_propose(int32_t n_params, int32_t n_temps, int32_t n_half, const double* x, const double* c,
+                           double a, uint64_t seed, uint64_t iteration, uint32_t half, const double* draws,
+                           double* q_out, double* z_out, void* stream) {
+    if (const char* m = pt_bad_shape(n_params, n_temps, n_half, n_half))
+        return fail(-1, std::string("rvm_pt_stretch_propose: ") + m);
+    if (half > 1u) return fail(-1, "rvm_pt_stretch_propose: half must be 0 or 1");
+    if (!(a > 1.0)) return fail(-1, "rvm_pt_stretch_propose: stretch scale a must be > 1");
+    if (!x || !c || !q_out || !z_out) return fail(-1, "rvm_pt_stretch_propose: null x, c, q_out or z_out");
+    hipError_t e = rvm::launch_pt_stretch_propose(n_params, n_temps, n_half, x, c, a, seed, iteration, half, draws,
+                                                  q_out, z_out, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rvm_pt_stretch_propose");
+}
+
+int rvm_pt_stretch_accept(int32_t n_params, int32_t n_temps, int32_t n_half, const double* betas, double* x,
+                          double* lnp, const double* q, const double* lnp_new, const double* z, uint64_t seed,
+                          uint64_t iteration, uint32_t half, const double* draws, int32_t* accepted, void* stream) {
+    if (const char* m = pt_bad_shape(n_params, n_temps, n_half, n_half))
+        return fail(-1, std::string("rvm_pt_stretch_accept: ") + m);
+    if (half > 1u) return fail(-1, "rvm_pt_stretch_accept: half must be 0 or 1");
+    if (!betas) return fail(-1, "rvm_pt_stretch_accept: null betas");
+    if (!x || !lnp || !q || !lnp_new || !z) return fail(-1, "rvm_pt_stretch_accept: null x, lnp, q, lnp_new or z");
+    hipError_t e = rvm::launch_pt_stretch_accept(n_params, n_temps, n_half, betas, x, lnp, q, lnp_new, z, seed,
+                                                 iteration, half, draws, accepted, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rvm_pt_stretch_accept");
+}
+
+int rvm_pt_swap(int32_t n_params, int32_t n_temps, int32_t n_half, const double* betas, double* x0, double* x1,
+                double* lnp0, double* lnp1, uint64_t seed, uint64_t iteration, const double* draws,
+                int32_t* swapped, void* stream) {
+    if (const char* m = pt_bad_shape(n_params, n_temps, n_half, 2 * (int64_t)n_half))
+        return fail(-1, std::string("rvm_pt_swap: ") + m);
+    if (n_temps == 1) return 0;  // one temperature has no neighbour: nothing to launch
+    if (!betas) return fail(-1, "rvm_pt_swap: null betas");
+    if (!x0 || !x1 || !lnp0 || !lnp1 || !swapped) return fail(-1, "rvm_pt_swap: null x0, x1, lnp0, lnp1 or swapped");
+    hipError_t e = rvm::launch_pt_swap(n_params, n_temps, n_half, betas, x0, x1, lnp0, lnp1, seed, iteration, draws,
+                                       swapped, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rvm_pt_swap");
 }
 
 int rvm_mh_propose(int32_t n_params, int32_t n_chains, int64_t chain_begin, const double* x, const double* scales,

@@ -12,6 +12,8 @@ enum : uint32_t {
     RNG_STRETCH_ACCEPT = 2,
     RNG_MH_PROPOSE = 3,
     RNG_MH_ACCEPT = 4,
+    // (5 and 6: SMALA, rvm_smala.hip)
+    RNG_PT_SWAP = 7,
 };
 
 // z = ((a - 1) u1 + 1)^2 / a  and  j = floor(u2 n1) (emcee _propose_stretch)
@@ -47,6 +49,24 @@ __device__ __forceinline__ bool stretch_accepts(int dim, double z, double lnp_ne
 #pragma clang fp contract(off)
     const double lnpdiff = (double)(dim - 1) * log(z) + lnp_new - lnp_old;
     return lnpdiff > log(u3);
+}
+
+// The tempered stretch accept of a walker at inverse temperature beta (rvm_tempering.hip):
+// lnpdiff = (dim - 1) * log(zz) + beta * newlnprob - beta * lnprob0, left to right.  beta = 1.0 gives
+// the bits of stretch_accepts; a -inf proposal is rejected (lnp_old is finite).
+__device__ __forceinline__ bool stretch_accepts_tempered(int dim, double z, double beta, double lnp_new,
+                                                         double lnp_old, double u3) {
+#pragma clang fp contract(off)
+    const double lnpdiff = (double)(dim - 1) * log(z) + beta * lnp_new - beta * lnp_old;
+    return lnpdiff > log(u3);
+}
+
+// Parallel-tempering exchange of the walkers at inverse temperatures beta_cold > beta_hot
+// (rvm_tempering.hip): d = (beta_cold - beta_hot) * (lnp_hot - lnp_cold) ; swap = d > log(rand)
+__device__ __forceinline__ bool pt_swaps(double beta_cold, double beta_hot, double lnp_cold, double lnp_hot, double u) {
+#pragma clang fp contract(off)
+    const double d = (beta_cold - beta_hot) * (lnp_hot - lnp_cold);
+    return d > log(u);
 }
 
 // ---- Gaussian random-walk MH (mcmc.py:89-121), shared by rvm_mh_propose / rvm_mh_accept and the

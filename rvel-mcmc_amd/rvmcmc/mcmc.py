@@ -299,5 +299,7 @@ class MhChains:
 
 
 from .smala import Alsmala, Smala, SmalaChains  # noqa: E402  (re-export with the reference's module layout)
+from .tempering import PTSampler  # noqa: E402
 
-__all__ = ["Mcmc", "lnprob", "Ensemble", "Mh", "MhChains", "Smala", "Alsmala", "SmalaChains", "EnsembleSampler"]
+__all__ = ["Mcmc", "lnprob", "Ensemble", "Mh", "MhChains", "Smala", "Alsmala", "SmalaChains", "EnsembleSampler",
+           "PTSampler"]
