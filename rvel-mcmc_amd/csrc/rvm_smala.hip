@@ -58,6 +58,7 @@ __device__ __forceinline__ void smala_metric_stage(int P, int C, int c, int lane
         constexpr int EPL = (PM * PM + 63) / 64;  // matrix entries per lane
         const int N2 = (P + 1) & ~1;
         const int PP = P * P;
+        bool done = false;  // converged, or given up on non-finite sums (uniform over the wave)
         for (int sweep = 0; sweep < 60; sweep++) {
             double off = 0.0, dia = 0.0;
             for (int idx = lane; idx < PP; idx += 64) {
@@ -68,7 +69,15 @@ __device__ __forceinline__ void smala_metric_stage(int P, int C, int c, int lane
             }
             off = wave_sum(off);
             dia = wave_sum(dia);
-            if (!(off > 1e-32 * dia)) break;  // converged (or NaN: caught by the SoftAbs check)
+            if (!(isfinite(off) && isfinite(dia))) {  // NaN, or squares past the double range: inf > inf
+                okflag = 0;                           // would read as converged
+                done = true;
+                break;
+            }
+            if (!(off > 1e-32 * dia)) {  // converged
+                done = true;
+                break;
+            }
             for (int r = 0; r < N2 - 1; r++) {
                 if (lane < N2 / 2) {
                     int a, b;
@@ -136,6 +145,7 @@ __device__ __forceinline__ void smala_metric_stage(int P, int C, int c, int lane
                 __syncthreads();
             }
         }
+        if (!done) okflag = 0;  // the sweep cap ran out: A is not diagonal, the cache is not usable
     }
     // SoftAbs (mcmc.py:135-139): lambda~ = lambda coth(alpha lambda), 1/alpha where |alpha lambda| < 1e-8
     if (lane < P) {
@@ -145,7 +155,16 @@ __device__ __forceinline__ void smala_metric_stage(int P, int C, int c, int lane
         lt[lane] = l;
         inv[lane] = 1.0 / l;
         if (!(isfinite(l) && l > 0.0)) okflag = 0;
+        // Eigenvector lane back to unit length.  A rotation whose tangent is below sqrt(ulp) has
+        // cs = 1 and sn = t after rounding, so it stretches its two columns by t^2/2 every time, never
+        // shrinks them; over the late sweeps of a graded matrix the squared norms drift up by ~100 ulp
+        // (the angles between columns stay within ~10), which is all of G's error there.
+        double n2 = 0.0;
+        for (int i = 0; i < P; i++) n2 += Qm[i * P + lane] * Qm[i * P + lane];
+        dn[lane] = isfinite(n2) && n2 > 0.0 ? 1.0 / sqrt(n2) : 1.0;
     }
+    __syncthreads();
+    for (int idx = lane; idx < P * P; idx += 64) Qm[idx] *= dn[idx % P];
     __syncthreads();
     // G = Q diag(lambda~) Q^T (out) and G^-1 = Q diag(1/lambda~) Q^T (into A)
     for (int idx = lane; idx < ntri; idx += 64) {

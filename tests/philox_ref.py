@@ -36,6 +36,19 @@ RNG_STRETCH_PROPOSE = 1
 RNG_STRETCH_ACCEPT = 2
 RNG_MH_PROPOSE = 3
 RNG_MH_ACCEPT = 4
+RNG_SMALA_PROPOSE = 5
+RNG_SMALA_ACCEPT = 6
+RNG_PT_SWAP = 7
+
+
+def normal(seed, item, iteration, stream_base, p):
+    """The N(0,1) draw of parameter p (streams RNG_MH_PROPOSE / RNG_SMALA_PROPOSE | p << 8):
+    Box-Muller sqrt(-2 ln u0) cos(2 pi u1) of the restated uniforms, evaluated at 40 digits."""
+    import mpmath as mp
+
+    u0, u1 = uniform2(seed, item, iteration, stream_base | (p << 8))
+    with mp.workdps(40):
+        return float(mp.sqrt(-2 * mp.log(mp.mpf(u0))) * mp.cos(2 * mp.pi * mp.mpf(u1)))
 
 
 def uniform2_vec(seed, items, iteration, stream):

@@ -10,6 +10,7 @@ import pytest
 
 import oracle as O
 from conftest import S2_PLANETS, S2_SCALES, s2_obs_oracle
+from smala_ref import metric_numpy as _smala_numpy
 
 pytestmark = pytest.mark.gpu
 
@@ -369,18 +370,6 @@ def test_smala_chains_run():
     assert sm.iteration == 5
     assert np.isfinite(sm.cache["lp"].cpu().numpy()).all()
     assert int(sm.accepted.sum()) > 0
-
-
-def _smala_numpy(lp, g, H, x, alpha, eps):
-    """mcmc.py:135-150 restated in numpy for one chain: SoftAbs metric, G^-1, chol, drift."""
-    lam, Q = np.linalg.eigh(-0.5 * (H + H.T))
-    with np.errstate(divide="ignore", invalid="ignore"):
-        lt = np.where(np.abs(alpha * lam) < 1e-8, 1.0 / alpha, lam / np.tanh(alpha * lam))
-    G = Q @ np.diag(lt) @ Q.T
-    Ginv = Q @ np.diag(1.0 / lt) @ Q.T
-    L = np.linalg.cholesky(Ginv)
-    mu = x + eps ** 2 * Ginv @ g / 2.0
-    return dict(G=G, Ginv=Ginv, L=L, mu=mu, logdet=float(np.sum(np.log(1.0 / lt))))
 
 
 def test_smala_derive_matches_numpy_softabs():
