@@ -168,6 +168,15 @@ int rvm_plan_faults(rvm_plan* plan, int32_t reset, int64_t* handoff_timeouts, in
  * (RVM_STATUS_SKIPPED); entries past RVM_N_COUNTERS read 0. */
 #define RVM_N_COUNTERS 7
 int rvm_plan_counters(rvm_plan* plan, int32_t reset, int64_t* out, int32_t n, void* stream);
+/* Hedged pass 2 (fused stretch launches whose likelihood grid leaves CUs idle run the
+ * second halving pass of the walker slots with the quickest pericentre passages beside the likelihood
+ * kernel): since the last reset, hedged = walker slots hedged, replayed = pass-2 walker-directions the
+ * refinement kernel took from the hedge, missed = pass-2 walker-directions of hedged launches it integrated
+ * itself (not hedged, or not complete in time).  Whether a result is ready in time depends on timing:
+ * these are kept apart from rvm_plan_counters, whose values do not.  Any pointer may be NULL; all zero on
+ * a plan without a hedge (RVM_HEDGE=0).  Synchronises the stream. */
+int rvm_plan_hedge_stats(rvm_plan* plan, int32_t reset, int64_t* hedged, int64_t* replayed, int64_t* missed,
+                         void* stream);
 /* Kernel timing (benchmarks): the plan's next max_launches likelihood evaluations (any entry point)
  * record HIP events on their stream around the likelihood kernel and around the refinement kernel
  * that follows it (0..4096; 0 stops).  rvm_plan_kernel_times waits for those events and returns

@@ -28,9 +28,14 @@
 
 namespace rvm {
 hipError_t launch_logl(const DevPlan& P, int W, const double* params, double hill_factor, unsigned long long* slots,
-                       double* logl, int32_t* status, double* rv_out, const StretchArgs& sa, hipStream_t stream);
+                       double* logl, int32_t* status, double* rv_out, const StretchArgs& sa, hipStream_t stream,
+                       int* dry_blocks);
 hipError_t launch_refine(const DevPlan& P, int W, const double* params, double hill_factor, double* logl,
-                         int32_t* status, double* rv_out, const StretchArgs& sa, int eager, hipStream_t stream);
+                         int32_t* status, double* rv_out, const StretchArgs& sa, int eager, int hedge,
+                         hipStream_t stream);
+int hedge_groups(const DevPlan& P, int W, int logl_blocks);
+hipError_t launch_hedge(const DevPlan& P, int W, double hill_factor, const StretchArgs& sa, int ngrp,
+                        hipStream_t stream);
 hipError_t launch_eager(const DevPlan& P, int W, const double* params, double hill_factor, hipStream_t stream);
 hipError_t launch_gen_bump(const DevPlan& P, hipStream_t stream);
 hipError_t prepare_logl(const DevPlan& P);
@@ -102,15 +107,16 @@ struct rvm_plan {
     mutable std::vector<hipEvent_t> tev;
     mutable int32_t tcap = 0, tn = 0;
     void* emem = nullptr;                // eager passes' results (DevPlan::rve, esum), small plans
+    void* hmem = nullptr;                // hedged pass 2's results and words (DevPlan::hrv ... hw)
     hipStream_t side = nullptr;          // their stream, forked from and joined to the caller's
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 };
 
 // One likelihood evaluation as every entry point runs it: the likelihood kernel, then (adaptive
 // plans) the refinement kernel for the walkers it handed on, stream-ordered.  Everything it enqueues
-// is complete when the caller's stream is (the header's conventions): an eager launch forks the
-// plan's side stream from the caller's and joins it back after the refinement kernel, which by then
-// has stopped every eager block it did not wait for (rvm_refine.hip).  No host-side state changes
+// is complete when the caller's stream is (the header's conventions): an eager or hedged launch forks
+// the plan's side stream from the caller's and joins it back after the refinement kernel, which by then
+// has stopped every eager or hedge block it did not wait for (rvm_refine.hip).  No host-side state changes
 // per launch -- the launch generation lives on the device -- so a captured hipGraph replays it.
 static hipError_t run_logl(const rvm_plan* plan, int W, const double* params, double hill_factor, double* logl,
                            int32_t* status, double* rv_out, const rvm::StretchArgs& sa, hipStream_t st) {
@@ -120,10 +126,22 @@ static hipError_t run_logl(const rvm_plan* plan, int W, const double* params, do
     const int eager = plan->side != nullptr && !mapped && rv_out == nullptr && params != nullptr &&
                       W >= rvm::RVM_EAGER_MIN && W <= plan->dev.eager_max;
     hipError_t e = hipSuccess;
-    if (eager) {
+    // hedged pass 2 (rvm_refine_impl.h hedge_kernel): fused stretch launches (half-steps, speculative
+    // iterations) whose likelihood grid leaves at least two CUs idle -- halving pass 2 of the slots with
+    // the quickest pericentre passages on the side stream, two CUs per group of them
+    int hgrp = 0;
+    if (plan->side != nullptr && plan->dev.hedge_groups > 0 && sa.c != nullptr && rv_out == nullptr && !eager) {
+        int nblk = 0;
+        if (rvm::launch_logl(plan->dev, W, params, hill_factor, plan->slots, logl, status, rv_out, sa, st, &nblk) ==
+            hipSuccess)
+            hgrp = rvm::hedge_groups(plan->dev, W, nblk);
+    }
+    if (eager || hgrp > 0) {
         e = hipEventRecord(plan->ev_fork, st);
         if (e == hipSuccess) e = hipStreamWaitEvent(plan->side, plan->ev_fork, 0);
-        if (e == hipSuccess) e = rvm::launch_eager(plan->dev, W, params, hill_factor, plan->side);
+        if (e == hipSuccess)
+            e = eager ? rvm::launch_eager(plan->dev, W, params, hill_factor, plan->side)
+                      : rvm::launch_hedge(plan->dev, W, hill_factor, sa, hgrp, plan->side);
         if (e != hipSuccess) {
             // (join whatever was enqueued on the side stream before reporting)
             if (hipEventRecord(plan->ev_join, plan->side) == hipSuccess) (void)hipStreamWaitEvent(st, plan->ev_join, 0);
@@ -131,14 +149,15 @@ static hipError_t run_logl(const rvm_plan* plan, int W, const double* params, do
         }
     }
     if (tm) (void)hipEventRecord(plan->tev[3 * plan->tn], st);
-    e = rvm::launch_logl(plan->dev, W, params, hill_factor, plan->slots, logl, status, rv_out, sa, st);
+    e = rvm::launch_logl(plan->dev, W, params, hill_factor, plan->slots, logl, status, rv_out, sa, st, nullptr);
     if (tm) (void)hipEventRecord(plan->tev[3 * plan->tn + 1], st);
     // (the refinement kernel runs even after a failed likelihood launch: it resets the work lists)
-    const hipError_t er = rvm::launch_refine(plan->dev, W, params, hill_factor, logl, status, rv_out, sa, eager, st);
+    const hipError_t er =
+        rvm::launch_refine(plan->dev, W, params, hill_factor, logl, status, rv_out, sa, eager, 2 * hgrp, st);
     if (e == hipSuccess) e = er;
     if (tm) (void)hipEventRecord(plan->tev[3 * plan->tn + 2], st);
     if (tm) plan->tn++;
-    if (eager) {
+    if (eager || hgrp > 0) {
         hipError_t ej = hipEventRecord(plan->ev_join, plan->side);
         if (ej == hipSuccess) ej = hipStreamWaitEvent(st, plan->ev_join, 0);
         if (ej == hipSuccess) ej = rvm::launch_gen_bump(plan->dev, st);
@@ -581,12 +600,60 @@ int rvm_plan_create(const rvm_config* cfg, const double* t, const double* rv, co
     // events -- only for plans that can make such a launch (a one-walker scalar plan never does, and
     // its stream would only add to the hardware queues).  Any failure: no eager passes,
     // the refinement kernel integrates as usual.
+    // Hedged pass 2 of fused stretch launches (rvm_refine_impl.h hedge_kernel) shares the side stream and
+    // the events: RVM_HEDGE=0 turns it off, RVM_HEDGE_GROUPS caps its groups (1 .. RVM_HEDGE_GROUPS_MAX;
+    // INTEGRATION.md).
+    P.hedge_groups = 0;
+    P.hrv = nullptr;
+    P.hsum = nullptr;
+    P.hslot = nullptr;
+    P.htab = nullptr;
+    P.hw = nullptr;
     {
         const char* eg = getenv("RVM_EAGER");  // (A/B knob: 0 turns the eager pass off, 1 on)
         const bool eager_on = eg ? eg[0] == '1' : RVM_EAGER_DEFAULT;
         const int emw = std::min<int>(max_walkers, rvm::RVM_EAGER_MAX);
-        if (P.rmax >= 2 && P.rvp != nullptr && P.gen_dev != nullptr && cfg->n_levels <= 4 && eager_on &&
-            max_walkers >= rvm::RVM_EAGER_MIN) {
+        const char* hg = getenv("RVM_HEDGE");
+        int hgroups = hg && hg[0] == '0' ? 0 : rvm::RVM_HEDGE_GROUPS_MAX;
+        if (const char* hn = getenv("RVM_HEDGE_GROUPS"))
+            hgroups = std::min(hgroups, std::max(0, std::min(atoi(hn), (int)rvm::RVM_HEDGE_GROUPS_MAX)));
+        if (hgroups > 0 && P.rmax >= 2 && P.rvp != nullptr && P.gen_dev != nullptr && cfg->n_levels <= 4 &&
+            max_walkers >= rvm::RVM_EAGER_MIN && P.n_cu >= 4) {
+            // RV [2][emax][stride], sums [2][3][stride], slots [2][stride], the per-slot table, the words
+            const size_t hs = rvm::RVM_HEDGE_STRIDE;
+            const size_t n_rv = 2 * (size_t)P.lvx_emax * hs, n_sum = 6 * hs, n_slot = 2 * hs;
+            const size_t n_all = n_rv + n_sum + n_slot + (size_t)max_walkers + rvm::RVM_HW_WORDS;
+            if (hipMalloc(&plan->hmem, n_all * sizeof(double)) == hipSuccess &&
+                hipMemset(plan->hmem, 0, n_all * sizeof(double)) == hipSuccess && hipDeviceSynchronize() == hipSuccess) {
+                P.hrv = reinterpret_cast<double*>(plan->hmem);
+                P.hsum = P.hrv + n_rv;
+                P.hslot = reinterpret_cast<unsigned long long*>(P.hsum + n_sum);
+                P.htab = P.hslot + n_slot;
+                P.hw = P.htab + max_walkers;
+                P.hedge_groups = hgroups;
+            } else {
+                (void)hipGetLastError();
+                if (plan->hmem) (void)hipFree(plan->hmem);
+                plan->hmem = nullptr;
+            }
+        }
+        const bool eager_plan = P.rmax >= 2 && P.rvp != nullptr && P.gen_dev != nullptr && cfg->n_levels <= 4 &&
+                                eager_on && max_walkers >= rvm::RVM_EAGER_MIN;
+        if (!eager_plan && P.hedge_groups > 0) {
+            // (no eager passes on this plan: the side stream and events for the hedge alone)
+            if (hipStreamCreateWithFlags(&plan->side, hipStreamNonBlocking) != hipSuccess ||
+                hipEventCreateWithFlags(&plan->ev_fork, hipEventDisableTiming) != hipSuccess ||
+                hipEventCreateWithFlags(&plan->ev_join, hipEventDisableTiming) != hipSuccess) {
+                (void)hipGetLastError();
+                if (plan->ev_fork) (void)hipEventDestroy(plan->ev_fork);
+                if (plan->ev_join) (void)hipEventDestroy(plan->ev_join);
+                if (plan->side) (void)hipStreamDestroy(plan->side);
+                plan->side = nullptr;
+                plan->ev_fork = plan->ev_join = nullptr;
+                P.hedge_groups = 0;
+            }
+        }
+        if (eager_plan) {
             // passes 1 and 2: RV [2][2][emax][stride], sums [2][2][3][stride]; flags [groups][8] (zeroed)
             const size_t plane = (size_t)P.lvx_emax * P.lvx_stride;
             const size_t nflag = rvm::RVM_EFLAG_WORDS * (size_t)((rvm::RVM_EAGER_MAX + 15) / 16) + 8;
@@ -610,6 +677,7 @@ int rvm_plan_create(const rvm_config* cfg, const double* t, const double* rv, co
                 plan->emem = nullptr;
                 plan->side = nullptr;
                 plan->ev_fork = plan->ev_join = nullptr;
+                P.hedge_groups = 0;  // (no side stream: no hedge either)
             }
         }
     }
@@ -641,6 +709,7 @@ void rvm_plan_destroy(rvm_plan* plan) {
     if (plan->ev_join) (void)hipEventDestroy(plan->ev_join);
     if (plan->side) (void)hipStreamDestroy(plan->side);
     if (plan->emem) (void)hipFree(plan->emem);
+    if (plan->hmem) (void)hipFree(plan->hmem);
     for (hipEvent_t ev : plan->tev) (void)hipEventDestroy(ev);
     if (plan->rqmem) (void)hipFree(plan->rqmem);
     if (plan->lvmem) (void)hipFree(plan->lvmem);
@@ -693,6 +762,24 @@ int rvm_plan_counters(rvm_plan* plan, int32_t reset, int64_t* out, int32_t n, vo
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) return hip_fail(e, "rvm_plan_counters: reset");
     }
+    return 0;
+}
+
+int rvm_plan_hedge_stats(rvm_plan* plan, int32_t reset, int64_t* hedged, int64_t* replayed, int64_t* missed,
+                         void* stream) {
+    if (!plan) return fail(-1, "rvm_plan_hedge_stats: null plan");
+    unsigned long long h[3] = {};
+    if (plan->dev.hw != nullptr) {
+        hipStream_t st = (hipStream_t)stream;
+        unsigned long long* d = plan->dev.hw + rvm::RVM_HW_STATS;
+        hipError_t e = hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && reset) e = hipMemsetAsync(d, 0, sizeof(h), st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return hip_fail(e, "rvm_plan_hedge_stats");
+    }
+    if (hedged) *hedged = (int64_t)h[0];
+    if (replayed) *replayed = (int64_t)h[1];
+    if (missed) *missed = (int64_t)h[2];
     return 0;
 }
 

@@ -63,6 +63,21 @@ constexpr int RVM_TEAMS_MAX = 4;
 constexpr int RVM_TEAMS_DEFAULT = 4;
 // ... and no more than the deepest pass of the plan's last this-many launches needed (at least two)
 constexpr int RVM_DEPTH_WINDOW = 8;
+// hedged pass 2 (rvm_refine_impl.h hedge_kernel): fused stretch launches run halving pass 2 of the walker
+// slots with the quickest pericentre passages beside the likelihood kernel, on the CUs its grid leaves
+// idle -- at most this many groups of 64 / L slots, two blocks (directions) each, one block per CU
+constexpr int RVM_HEDGE_GROUPS_MAX = 8;
+// ... their results' row stride (8 groups of at most 64 slots), and one more group of candidates: the
+// best-ranked group is ranked but not hedged (launch_hedge_t)
+constexpr int RVM_HEDGE_STRIDE = 512;
+constexpr int RVM_HEDGE_CAND = RVM_HEDGE_STRIDE + 64;
+// ... launches of at most this many slots (every hedge block ranks all of them in its LDS, 8 B each)
+constexpr int RVM_HEDGE_MAX_W = 12288;
+// DevPlan::hw words: [0] cancel (generation << 8 | 1), [1] refinement blocks that have left,
+// [2 + 2 g + d] group g direction d complete (generation << 8 | 2), then the statistics: slots hedged,
+// pass-2 walker-directions replayed, pass-2 walker-directions integrated although the launch hedged
+constexpr int RVM_HW_STATS = 2 + 2 * RVM_HEDGE_GROUPS_MAX;
+constexpr int RVM_HW_WORDS = RVM_HW_STATS + 3 + 3;
 
 // Epoch schedule of one integration direction (t >= 0 ascending from 0, or t < 0 descending).
 struct DirSched {
@@ -178,10 +193,23 @@ struct DevPlan {
     int32_t eager_max;
     int32_t eager_passes;  // (1 or 2: how many halving passes eager_kernel runs)
     int32_t eager_split;   // 1: an eager launch's refinement runs each direction of a group on its own block
+    // hedged pass 2 (rvm_refine_impl.h hedge_kernel; fused stretch launches whose likelihood grid leaves
+    // CUs idle): hedge_groups the most groups a launch hedges (0: never; RVM_HEDGE, RVM_HEDGE_GROUPS);
+    // hrv [2 directions]
+    // [lvx_emax][RVM_HEDGE_STRIDE] pass 2's RV per epoch by hedge index, hsum [2][3][RVM_HEDGE_STRIDE] its
+    // chi2, estimate and encounter flag, hslot [2][RVM_HEDGE_STRIDE] the walker slot at each index
+    // (generation << 16 | slot),
+    // htab [rq_cap] per walker slot its hedge index (generation << 16 | index), hw [RVM_HW_WORDS]
+    int32_t hedge_groups;
+    double* hrv;
+    double* hsum;
+    unsigned long long* hslot;
+    unsigned long long* htab;
+    unsigned long long* hw;
     // the launch generation (device word, >= 1): the tag of the refinement kernel's exchange flags and
     // the eager blocks' claim words.  Read on the device by both kernels and advanced on the device
-    // after every launch (the refinement kernel's last block, or gen_bump_kernel after an eager
-    // launch), so a launch sequence captured into a hipGraph tags every replay afresh.
+    // after every launch (the refinement kernel's last block, or gen_bump_kernel after an eager or
+    // hedged launch), so a launch sequence captured into a hipGraph tags every replay afresh.
     unsigned long long* gen_dev;
     // plan-owned device counters (rvm_plan_faults): [0] level-split hand-offs given up (the
     // workspace is dirty until reset), [1] NONFINITE results, [2] UNRESOLVED results,

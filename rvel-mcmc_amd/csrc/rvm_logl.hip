@@ -1357,7 +1357,7 @@ static size_t lds_budget() {
 template <int NPV, bool D3V>
 static hipError_t launch_logl_t(const DevPlan& P, int W, const double* params, double hill_factor,
                                 unsigned long long* slots, double* logl, int32_t* status, double* rv_out,
-                                const StretchArgs& sa, hipStream_t stream) {
+                                const StretchArgs& sa, hipStream_t stream, int* dry_blocks) {
     const int lpw = LanesPerWalker<NPV>::value;
     const int wpb = 64 / lpw;
     const int groups = (W + wpb - 1) / wpb;
@@ -1439,6 +1439,10 @@ static hipError_t launch_logl_t(const DevPlan& P, int W, const double* params, d
             smem = smem_ls;
         }
     }
+    if (dry_blocks != nullptr) {  // (the grid this launch would take, nothing launched: run_logl's hedge)
+        *dry_blocks = (int)(grid.x * grid.y);
+        return hipSuccess;
+    }
     if (nA > 0) {
         logl_kernel<NPV, D3V, true><<<grid, block, smem, stream>>>(P, W, params, hill_factor, slots, rv_out, logl,
                                                                    status, sa, nA, tB | (splitA << 8) | (lsx << 9));
@@ -1494,12 +1498,13 @@ hipError_t prepare_logl(const DevPlan& P) {
 // finished by the refinement kernel (rvm_refine.hip launch_refine), which the caller enqueues next
 // on the same stream (rvm_abi.hip run_logl): every output is final when both have run
 hipError_t launch_logl(const DevPlan& P, int W, const double* params, double hill_factor, unsigned long long* slots,
-                       double* logl, int32_t* status, double* rv_out, const StretchArgs& sa, hipStream_t stream) {
+                       double* logl, int32_t* status, double* rv_out, const StretchArgs& sa, hipStream_t stream,
+                       int* dry_blocks) {
     const bool inc = P.inclined != 0;
     hipError_t e = hipErrorInvalidValue;
 #define RVM_LAUNCH(NPV) \
-    (inc ? launch_logl_t<NPV, true>(P, W, params, hill_factor, slots, logl, status, rv_out, sa, stream) \
-         : launch_logl_t<NPV, false>(P, W, params, hill_factor, slots, logl, status, rv_out, sa, stream))
+    (inc ? launch_logl_t<NPV, true>(P, W, params, hill_factor, slots, logl, status, rv_out, sa, stream, dry_blocks) \
+         : launch_logl_t<NPV, false>(P, W, params, hill_factor, slots, logl, status, rv_out, sa, stream, dry_blocks))
     switch (P.n_planets) {
         case 1:
             e = RVM_LAUNCH(1);

@@ -4,8 +4,8 @@
 
 namespace rvm {
 
-// After an eager launch (run_logl, once the side stream has joined): the next launch generation
-// (the refinement kernel advances it itself when no eager blocks share its generation)
+// After an eager or hedged launch (run_logl, once the side stream has joined): the next launch generation
+// (the refinement kernel advances it itself when no eager or hedge blocks share its generation)
 __global__ void gen_bump_kernel(unsigned long long* gen_dev) {
     if (threadIdx.x == 0) __hip_atomic_fetch_add(gen_dev, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -30,18 +30,51 @@ hipError_t launch_eager(const DevPlan& P, int W, const double* params, double hi
     }
 }
 
+// groups a hedged pass 2 of this fused stretch launch may take (rvm_refine_impl.h hedge_kernel; 0: none)
+int hedge_groups(const DevPlan& P, int W, int logl_blocks) {
+    switch (P.n_planets) {
+        case 1:
+            return hedge_groups_np1(P, W, logl_blocks);
+        case 2:
+            return hedge_groups_np2(P, W, logl_blocks);
+        case 3:
+            return hedge_groups_np3(P, W, logl_blocks);
+        case 4:
+            return hedge_groups_np4(P, W, logl_blocks);
+        default:
+            return 0;
+    }
+}
+
+hipError_t launch_hedge(const DevPlan& P, int W, double hill_factor, const StretchArgs& sa, int ngrp,
+                        hipStream_t stream) {
+    switch (P.n_planets) {
+        case 1:
+            return launch_hedge_np1(P, W, hill_factor, sa, ngrp, stream);
+        case 2:
+            return launch_hedge_np2(P, W, hill_factor, sa, ngrp, stream);
+        case 3:
+            return launch_hedge_np3(P, W, hill_factor, sa, ngrp, stream);
+        case 4:
+            return launch_hedge_np4(P, W, hill_factor, sa, ngrp, stream);
+        default:
+            return hipErrorInvalidValue;
+    }
+}
+
 hipError_t launch_refine(const DevPlan& P, int W, const double* params, double hill_factor, double* logl,
-                         int32_t* status, double* rv_out, const StretchArgs& sa, int eager, hipStream_t stream) {
+                         int32_t* status, double* rv_out, const StretchArgs& sa, int eager, int hedge,
+                         hipStream_t stream) {
     if (P.rmax <= 0 || P.rq_n == nullptr) return hipSuccess;
     switch (P.n_planets) {
         case 1:
-            return launch_refine_np1(P, W, params, hill_factor, logl, status, rv_out, sa, eager, stream);
+            return launch_refine_np1(P, W, params, hill_factor, logl, status, rv_out, sa, eager, hedge, stream);
         case 2:
-            return launch_refine_np2(P, W, params, hill_factor, logl, status, rv_out, sa, eager, stream);
+            return launch_refine_np2(P, W, params, hill_factor, logl, status, rv_out, sa, eager, hedge, stream);
         case 3:
-            return launch_refine_np3(P, W, params, hill_factor, logl, status, rv_out, sa, eager, stream);
+            return launch_refine_np3(P, W, params, hill_factor, logl, status, rv_out, sa, eager, hedge, stream);
         case 4:
-            return launch_refine_np4(P, W, params, hill_factor, logl, status, rv_out, sa, eager, stream);
+            return launch_refine_np4(P, W, params, hill_factor, logl, status, rv_out, sa, eager, hedge, stream);
         default:
             return hipErrorInvalidValue;
     }

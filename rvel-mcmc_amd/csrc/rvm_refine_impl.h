@@ -127,6 +127,13 @@ __device__ __forceinline__ unsigned long long pass_ticks(const DevPlan& P, int r
     return t < cap ? t : (P.spin_ticks > cap ? P.spin_ticks : cap);
 }
 
+// one direction of a walker between the passes: 1 open, 0 settled, 2 encounter, 3 non-finite pass; its
+// chi2 and lower bound; the previous pass's estimate, the best pass's and that pass's chi2
+struct DirState {
+    int open;
+    double chi, lb, pest, best, bchi;
+};
+
 // NW: waves per workgroup.  8 (512 threads) runs a both-direction group's two directions side by side
 // (mirrored levels) and plans of up to 8 levels; 4 (256 threads, plans of at most four levels) runs
 // them one after the other when a group holds both -- the split and team layouts, the steady state's,
@@ -137,7 +144,7 @@ template <int NP, bool D3, int NW>
 __global__ __launch_bounds__(NW * 64) void refine_kernel(const DevPlan P, const int W, const double* __restrict__ params,
                                                      const double hill_factor, double* __restrict__ rv_out,
                                                      double* __restrict__ logl_out, int32_t* __restrict__ status_out,
-                                                     const StretchArgs sa, const int eager) {
+                                                     const StretchArgs sa, const int eager, const int hedge) {
     constexpr int L = LanesPerWalker<NP>::value;
     constexpr int WPB = 64 / L;
     constexpr int PR = D3 ? 7 : 5;
@@ -190,7 +197,7 @@ __global__ __launch_bounds__(NW * 64) void refine_kernel(const DevPlan P, const 
 #endif
         if (done == (int)gridDim.x - 1) {
             for (int i = 0; i < 4; i++) __hip_atomic_store(P.rq_n + i, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (!eager) __hip_atomic_store(P.gen_dev, g0 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (!eager && !hedge) __hip_atomic_store(P.gen_dev, g0 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     __syncthreads();
@@ -206,9 +213,23 @@ __global__ __launch_bounds__(NW * 64) void refine_kernel(const DevPlan P, const 
     // after every pass; only when every task has a workgroup of its own in the grid (all co-resident
     // once dispatched; in-order dispatch leaves at most one workgroup waiting for its partner)
     const int ntask_split = 2 * gq0 + gq1 + gq2;
+    // (hedge: the launch's hedge blocks hold `hedge` CUs to themselves until they end or are cancelled --
+    // the tasks that wait for one another must fit the rest)
+    const int gfit = hedge && P.n_cu - hedge < (int)gridDim.x ? P.n_cu - hedge : (int)gridDim.x;
+    // the block's leave: the last one out cancels whatever hedge block still runs (the caller's stream
+    // joins them next, rvm_abi.hip run_logl)
+    auto leave = [&]() {
+        if (hedge && threadIdx.x == 0) {
+            gu64* hw = (gu64*)P.hw;
+            if (__hip_atomic_fetch_add(hw + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 == gridDim.x) {
+                __hip_atomic_store(hw + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(hw, (gen << 8) | 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    };
     // (eager: pass 1 is a replay of eager_kernel's results, both directions in one block)
     const bool split = !eager && P.rq_x != nullptr && gq0 <= P.rq_xgroups && ((int)gridDim.x & 1) == 0 &&
-                       ntask_split <= (int)gridDim.x;
+                       ntask_split <= gfit;
     // teams: team t runs pass t + 1 of the group from the start (A pass 1, B pass 2, C pass 3 ...), the
     // last one then the rest -- when the split layout holds, no RV curve is wanted (every team would
     // write it), and as many teams as the plan allows whose tasks all fit the grid (at least two), and
@@ -221,7 +242,7 @@ __global__ __launch_bounds__(NW * 64) void refine_kernel(const DevPlan P, const 
         ng <= P.rq_xgroups) {
         nteam = P.n_teams < P.rmax ? P.n_teams : P.rmax;
         if (nteam > (depth_hint > 2 ? depth_hint : 2)) nteam = depth_hint > 2 ? depth_hint : 2;
-        while (nteam >= 2 && nteam * ntask_split > (int)gridDim.x) nteam--;
+        while (nteam >= 2 && nteam * ntask_split > gfit) nteam--;
     }
     const bool team = nteam >= 2;
     const int ntask_team = nteam * ntask_split;
@@ -232,7 +253,10 @@ __global__ __launch_bounds__(NW * 64) void refine_kernel(const DevPlan P, const 
     const bool esplit = eager && P.eager_split && P.rq_x != nullptr && ngw <= P.rq_xgroups &&
                         ((int)gridDim.x & 1) == 0 && 2 * ngw <= (int)gridDim.x;
     const int ntask = eager ? (esplit ? 2 * ngw : ngw) : (team ? ntask_team : (split ? ntask_split : ng));
-    if ((int)blockIdx.x >= ntask) return;
+    if ((int)blockIdx.x >= ntask) {
+        leave();
+        return;
+    }
 
     // LDS: both directions' schedules ([d][seg_h1 | obs_rv | obs_s2 | (seg_n, obs_idx)], E_d each),
     // the levels' star vx per epoch (double-buffered), encounter flags, the lanes' state at t = 0,
@@ -259,7 +283,8 @@ __global__ __launch_bounds__(NW * 64) void refine_kernel(const DevPlan P, const 
     // eager tasks: the group's walker indices and each slot's list (-1: not listed, the likelihood
     // kernel finished it), and whether any slot is listed
     __shared__ int s_eitems[64], s_eli[64], s_eany;
-    __shared__ int s_emask;  // (eager) directions of the current pass an eager block runs
+    __shared__ int s_emask;  // (eager) directions of the current pass an eager block runs; (hedge) ran
+    __shared__ int s_hix[2][64];  // (hedge) the slots' hedge indices per direction
     __shared__ int s_skip[64];  // the slot is a speculative variant its partner's decision rules out
     const int emax = P.fwd.n_epochs > P.bwd.n_epochs ? P.fwd.n_epochs : P.bwd.n_epochs;
     for (int dd = 0; dd < 2; dd++) {
@@ -446,37 +471,109 @@ __global__ __launch_bounds__(NW * 64) void refine_kernel(const DevPlan P, const 
         // oracle/rvoracle.c dir_halve -- the last pass would run 2^rmax x the base steps),
         // settled (estimate within the bound), settled at the roundoff floor, or still open with the
         // pass's lower bound on its chi2
-        auto pass_result = [&](const int dd, const int rfp, const double c2, const double e2, const double d2,
-                               const int er) __attribute__((always_inline)) {
+        // (pass_eval: the rule on a copy of the direction's state, nothing stored or counted -- team A's
+        // trial of a hedged pass 2 below; returns whether the direction settled at its roundoff floor)
+        auto pass_eval = [&](DirState& q, const int rfp, const double c2, const double e2, const double d2,
+                             const int er) __attribute__((always_inline)) -> bool {
             const bool fin = isfinite(c2) && isfinite(e2);
             if (!er && !fin) {
-                s_open[dd][lane] = 3;
-                return;
+                q.open = 3;
+                return false;
             }
             const double en = e2 / P.npoints;
             // (the roundoff floor: this pass's estimate no longer falls; the best pass's estimate is
             // e2 / npoints units too)
-            const bool stall = fin && rfp >= 2 && !(en < 0.5 * s_pest[dd][lane]);
-            if (fin && en < s_best[dd][lane]) {
-                s_best[dd][lane] = en;
-                s_bchi[dd][lane] = c2;
+            const bool stall = fin && rfp >= 2 && !(en < 0.5 * q.pest);
+            if (fin && en < q.best) {
+                q.best = en;
+                q.bchi = c2;
             }
-            s_pest[dd][lane] = fin ? en : INFINITY;
+            q.pest = fin ? en : INFINITY;
             if (er) {
-                s_open[dd][lane] = 2;
+                q.open = 2;
             } else if (fin && !(en > P.rtol_dir)) {
-                s_open[dd][lane] = 0;
-                s_chi[dd][lane] = c2;
-                s_lb[dd][lane] = c2;
-            } else if (stall && s_best[dd][lane] <= RVM_FLOOR_BOUND * P.rtol_dir) {
-                s_open[dd][lane] = 0;
-                s_chi[dd][lane] = s_bchi[dd][lane];
-                s_lb[dd][lane] = s_bchi[dd][lane];
-                __hip_atomic_fetch_add(P.counters + 5, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                q.open = 0;
+                q.chi = c2;
+                q.lb = c2;
+            } else if (stall && q.best <= RVM_FLOOR_BOUND * P.rtol_dir) {
+                q.open = 0;
+                q.chi = q.bchi;
+                q.lb = q.bchi;
+                return true;
             } else {
-                s_chi[dd][lane] = fin ? c2 : __builtin_nan("");
-                s_lb[dd][lane] = fin ? open_lb(c2, d2, e2) : 0.0;
+                q.chi = fin ? c2 : __builtin_nan("");
+                q.lb = fin ? open_lb(c2, d2, e2) : 0.0;
             }
+            return false;
+        };
+        auto dir_load = [&](const int dd) __attribute__((always_inline)) {
+            return DirState{s_open[dd][lane], s_chi[dd][lane], s_lb[dd][lane], s_pest[dd][lane], s_best[dd][lane],
+                            s_bchi[dd][lane]};
+        };
+        auto dir_store = [&](const int dd, const DirState& q, const bool floor) __attribute__((always_inline)) {
+            s_open[dd][lane] = q.open;
+            s_chi[dd][lane] = q.chi;
+            s_lb[dd][lane] = q.lb;
+            s_pest[dd][lane] = q.pest;
+            s_best[dd][lane] = q.best;
+            s_bchi[dd][lane] = q.bchi;
+            if (floor) __hip_atomic_fetch_add(P.counters + 5, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        };
+        auto pass_result = [&](const int dd, const int rfp, const double c2, const double e2, const double d2,
+                               const int er) __attribute__((always_inline)) {
+            DirState q = dir_load(dd);
+            const bool floor = pass_eval(q, rfp, c2, e2, d2, er);
+            dir_store(dd, q, floor);
+        };
+        // the walker's decision from its directions' states after pass rfd: whether it is done, and then
+        // its status, logl and the directions a certain reject cut short
+        auto decide = [&](const DirState& qf, const DirState& qb, const int rfd, int& stw, double& lp,
+                          int& ncut) __attribute__((always_inline)) -> bool {
+            const int of = qf.open, ob = qb.open;
+            stw = RVM_STATUS_OK;
+            lp = 0.0;
+            ncut = 0;
+            if (s_xfault) {
+                stw = RVM_STATUS_NONFINITE;
+            } else if (of >= 2 || ob >= 2) {
+                // (the forward direction's end first, as the oracle integrates it first)
+                stw = (of >= 2 ? of : ob) == 2 ? RVM_STATUS_ENCOUNTER : RVM_STATUS_NONFINITE;
+            } else if (of == 0 && ob == 0) {
+                lp = -((qb.chi + qf.chi) / P.npoints);  // state.py:98, 109
+                if (!isfinite(lp)) stw = RVM_STATUS_NONFINITE;
+            } else {
+                const double lp_hi = -((qb.lb + qf.lb) / P.npoints);
+                const int dmode = s_dmode[lane];
+                if (dmode != 0 && isfinite(lp_hi) &&
+                    !accepts_at(sa, dmode, s_acc[0][lane], s_acc[1][lane], s_acc[2][lane], lp_hi)) {
+                    lp = lp_hi;  // a certain reject
+                    ncut = (of ? 1 : 0) + (ob ? 1 : 0);
+                } else if (rfd == P.rmax) {
+                    stw = RVM_STATUS_UNRESOLVED;
+                } else {
+                    return false;
+                }
+            }
+            return true;
+        };
+        // (hedge) walker slot `lane`'s hedge index when the launch's hedge holds pass 2 of its direction dd
+        // complete (the group's completion word of this generation, then the slot stored at the index, tagged
+        // with the generation too: a
+        // hedge block that ranked the slots differently from its partner never passes for it), else -1.
+        // Never waits.
+        auto hedge_index = [&](const int dd, const bool want) __attribute__((always_inline)) -> int {
+            if (!want) return -1;
+            const unsigned long long tb = __hip_atomic_load((gu64*)P.htab + wme, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int ix = (int)(tb & 0xFFFF);
+            if ((tb >> 16) != gen || ix >= RVM_HEDGE_STRIDE || ix / WPB >= RVM_HEDGE_GROUPS_MAX) return -1;
+            if (__hip_atomic_load((gu64*)P.hw + 2 + 2 * (ix / WPB) + dd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) !=
+                ((gen << 8) | 2ull))
+                return -1;
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            if (__hip_atomic_load((gu64*)P.hslot + (size_t)dd * RVM_HEDGE_STRIDE + ix, __ATOMIC_RELAXED,
+                                  __HIP_MEMORY_SCOPE_AGENT) != ((gen << 16) | (unsigned long long)wme))
+                return -1;
+            return ix;
         };
         bool finisher = !team && own <= 0;  // the workgroup that finishes the walkers
         int rf_last = 0;                    // the last pass the group's decisions took
@@ -504,6 +601,34 @@ __global__ __launch_bounds__(NW * 64) void refine_kernel(const DevPlan P, const 
                             em |= 1 << d3;
                     }
                     s_emask = em;
+                }
+                __syncthreads();
+                emask = s_emask;
+            }
+            // (hedge; the layouts without teams) pass 2 of a direction whose every open walker has its
+            // hedge result complete is replayed from it below, as an eager pass is; else integrated
+            const bool hrep = hedge && !eager && !team && rf == 2;
+            if (hrep) {
+                if (wv == 0) {
+                    const bool o0 = lane < WPB && ((mk0 >> lane) & 1) && own != 1;
+                    const bool o1 = lane < WPB && ((mk1 >> lane) & 1) && own != 0;
+                    const int i0 = hedge_index(0, o0), i1 = hedge_index(1, o1);
+                    const uint64_t n0 = ballot(o0), n1 = ballot(o1);
+                    const uint64_t x0 = ballot(o0 && i0 < 0), x1 = ballot(o1 && i1 < 0);
+                    if (lane < WPB) {
+                        s_hix[0][lane] = i0;
+                        s_hix[1][lane] = i1;
+                    }
+                    if (lane == 0) {
+                        const int em = (n0 && !x0 ? 1 : 0) | (n1 && !x1 ? 2 : 0);
+                        s_emask = em;
+                        const unsigned long long nr = ((em & 1) ? __builtin_popcountll(n0) : 0) +
+                                                      ((em & 2) ? __builtin_popcountll(n1) : 0);
+                        const unsigned long long nm = __builtin_popcountll(n0) + __builtin_popcountll(n1) - nr;
+                        gu64* hst = (gu64*)P.hw + RVM_HW_STATS;
+                        if (nr) __hip_atomic_fetch_add(hst + 1, nr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (nm) __hip_atomic_fetch_add(hst + 2, nm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
                 }
                 __syncthreads();
                 emask = s_emask;
@@ -668,12 +793,13 @@ __global__ __launch_bounds__(NW * 64) void refine_kernel(const DevPlan P, const 
                 // RV (P.rvp: the main pass's, then pass 1's), which this pass's RV then replaces there
                 const bool mine0 = (emask & 1) && lane < WPB && ((mk0 >> lane) & 1);
                 const bool mine1 = (emask & 2) && lane < WPB && ((mk1 >> lane) & 1);
-                gu64* f0 = ef + 2 + 2 * (rf - 1);
+                // (hedge: the directions' results were found complete above -- no wait)
+                gu64* f0 = hrep ? nullptr : ef + 2 + 2 * (rf - 1);
                 const unsigned long long done = (gen << 8) | 2ull;
                 SpinClock clk;
                 clk.restart();
                 bool ok = true;
-                for (;;) {
+                for (; !hrep;) {
                     const bool rdy = (!mine0 || __hip_atomic_load(f0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == done) &&
                                      (!mine1 || __hip_atomic_load(f0 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == done);
                     if (ballot(!rdy) == 0) break;
@@ -699,7 +825,10 @@ __global__ __launch_bounds__(NW * 64) void refine_kernel(const DevPlan P, const 
                         const double* b_rv = b_dir + Eb;
                         const double* b_s2 = b_dir + 2 * Eb;
                         const size_t plane = (size_t)P.lvx_emax * P.lvx_stride;
-                        gu64* cur = (gu64*)(P.rve + ((size_t)(rf - 1) * 2 + d3) * plane + wme);
+                        // (hedge: its buffers, by the slot's hedge index)
+                        const size_t cst = hrep ? (size_t)RVM_HEDGE_STRIDE : (size_t)P.lvx_stride;
+                        gu64* cur = hrep ? (gu64*)(P.hrv + (size_t)d3 * P.lvx_emax * RVM_HEDGE_STRIDE + s_hix[d3][lane])
+                                         : (gu64*)(P.rve + ((size_t)(rf - 1) * 2 + d3) * plane + wme);
                         double* prv = P.rvp + (size_t)d3 * plane + wme;
                         double d2 = 0.0;
                         // (RCH epochs' loads in flight at once: one epoch at a time, each store
@@ -711,7 +840,7 @@ __global__ __launch_bounds__(NW * 64) void refine_kernel(const DevPlan P, const 
                             for (int j = 0; j < RCH; j++) {
                                 const int e = e0 + j < Eb ? e0 + j : Eb - 1;
                                 rvc[j] = __longlong_as_double((long long)__hip_atomic_load(
-                                    cur + (size_t)e * P.lvx_stride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                                    cur + (size_t)e * cst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
                                 pvc[j] = prv[(size_t)e * P.lvx_stride];
                             }
 #pragma unroll
@@ -725,12 +854,13 @@ __global__ __launch_bounds__(NW * 64) void refine_kernel(const DevPlan P, const 
                                 }
                             }
                         }
-                        gu64* es = (gu64*)(P.esum + ((size_t)(rf - 1) * 2 + d3) * 3 * P.lvx_stride + wme);
+                        gu64* es = hrep ? (gu64*)(P.hsum + (size_t)d3 * 3 * RVM_HEDGE_STRIDE + s_hix[d3][lane])
+                                        : (gu64*)(P.esum + ((size_t)(rf - 1) * 2 + d3) * 3 * P.lvx_stride + wme);
                         auto ld = [&](size_t o) {
                             return __longlong_as_double((long long)__hip_atomic_load(es + o, __ATOMIC_RELAXED,
                                                                                      __HIP_MEMORY_SCOPE_AGENT));
                         };
-                        pass_result(d3, rf, ld(0), ld(P.lvx_stride), d2, (int)ld(2 * (size_t)P.lvx_stride));
+                        pass_result(d3, rf, ld(0), ld(cst), d2, (int)ld(2 * cst));
                     }
                 }
                 if (lane == 0) {
@@ -902,43 +1032,97 @@ __global__ __launch_bounds__(NW * 64) void refine_kernel(const DevPlan P, const 
             if (wv == 0) {
                 bool live = lane < WPB && s_live[lane] != 0;
                 if (live) {
-                    const int of = s_open[0][lane], ob = s_open[1][lane];
-                    int stw = RVM_STATUS_OK;
-                    double lp = 0.0;
-                    bool done = true;
-                    if (s_xfault) {
-                        stw = RVM_STATUS_NONFINITE;
-                    } else if (of >= 2 || ob >= 2) {
-                        // (the forward direction's end first, as the oracle integrates it first)
-                        stw = (of >= 2 ? of : ob) == 2 ? RVM_STATUS_ENCOUNTER : RVM_STATUS_NONFINITE;
-                    } else if (of == 0 && ob == 0) {
-                        lp = -((s_chi[1][lane] + s_chi[0][lane]) / P.npoints);  // state.py:98, 109
-                        if (!isfinite(lp)) stw = RVM_STATUS_NONFINITE;
-                    } else {
-                        const double lp_hi = -((s_lb[1][lane] + s_lb[0][lane]) / P.npoints);
-                        const int dmode = s_dmode[lane];
-                        if (dmode != 0 && isfinite(lp_hi) &&
-                            !accepts_at(sa, dmode, s_acc[0][lane], s_acc[1][lane], s_acc[2][lane], lp_hi)) {
-                            lp = lp_hi;  // a certain reject
-                            if (own <= 0)
-                                __hip_atomic_fetch_add(P.counters + 4,
-                                                       (unsigned long long)((of ? 1 : 0) + (ob ? 1 : 0)),
-                                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        } else if (rf == P.rmax) {
-                            stw = RVM_STATUS_UNRESOLVED;
-                        } else {
-                            done = false;
-                        }
-                    }
-                    if (done) {
+                    int stw, ncut;
+                    double lp;
+                    if (decide(dir_load(0), dir_load(1), rf, stw, lp, ncut)) {
+                        if (ncut && own <= 0)
+                            __hip_atomic_fetch_add(P.counters + 4, (unsigned long long)ncut, __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT);
                         live = false;
                         s_live[lane] = 0;
                         s_stw[lane] = stw;
                         s_lpw[lane] = stw == RVM_STATUS_OK ? lp : -INFINITY;
                     }
                 }
-                const uint64_t m0 = ballot(live && s_open[0][lane] == 1);
-                const uint64_t m1 = ballot(live && s_open[1][lane] == 1);
+                uint64_t m0 = ballot(live && s_open[0][lane] == 1);
+                uint64_t m1 = ballot(live && s_open[1][lane] == 1);
+                if (hedge && team && tm == 0 && rf == 1 && own <= 0 && P.rmax >= 2 && (m0 | m1) != 0) {
+                    // (hedge) team A with walkers left for pass 2: when the launch's hedge holds that pass
+                    // complete for every open direction of theirs, try it on copies of the state this team
+                    // would publish -- what team B would apply: pass 2's chi2, estimate and encounter flag,
+                    // the step-doubling change against pass 1's RV (write-through, both directions: the
+                    // split exchange has ordered the partner's) -- and if that ends every walker, take it:
+                    // the group is done and team B stops.  Else nothing changes and team B goes on.
+                    const bool o0 = live && s_open[0][lane] == 1, o1 = live && s_open[1][lane] == 1;
+                    const int hi[2] = {hedge_index(0, o0), hedge_index(1, o1)};
+                    bool took = false;
+                    if (ballot((o0 && hi[0] < 0) || (o1 && hi[1] < 0)) == 0) {
+                        DirState q[2] = {dir_load(0), dir_load(1)};
+                        bool fl[2] = {false, false};
+                        for (int d3 = 0; d3 < 2; d3++) {
+                            if (!(d3 ? o1 : o0)) continue;
+                            const int Eb = (d3 ? P.bwd : P.fwd).n_epochs;
+                            const double* b_dir = s_sched + (size_t)d3 * 4 * emax;
+                            const double* b_rv = b_dir + Eb;
+                            const double* b_s2 = b_dir + 2 * Eb;
+                            const gu64* cur = (const gu64*)(P.hrv + (size_t)d3 * P.lvx_emax * RVM_HEDGE_STRIDE + hi[d3]);
+                            const gu64* prv = (const gu64*)(P.rvp + (size_t)d3 * P.lvx_emax * P.lvx_stride + wme);
+                            double d2 = 0.0;
+                            constexpr int RCH = 16;  // (epochs' loads in flight at once, as the eager replay)
+                            for (int e0 = 0; e0 < Eb; e0 += RCH) {
+                                double rvc[RCH], pvc[RCH];
+#pragma unroll
+                                for (int j = 0; j < RCH; j++) {
+                                    const int e = e0 + j < Eb ? e0 + j : Eb - 1;
+                                    rvc[j] = __longlong_as_double((long long)__hip_atomic_load(
+                                        cur + (size_t)e * RVM_HEDGE_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                                    pvc[j] = __longlong_as_double((long long)__hip_atomic_load(
+                                        prv + (size_t)e * P.lvx_stride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                                }
+#pragma unroll
+                                for (int j = 0; j < RCH; j++) {
+                                    const int e = e0 + j;
+                                    if (e < Eb) {
+                                        const double rvx = rvc[j], pv = pvc[j];
+                                        const double r = rvx - b_rv[e];
+                                        d2 += fabs((rvx - pv) * (r + (pv - b_rv[e]))) / b_s2[e];
+                                    }
+                                }
+                            }
+                            const gu64* es = (const gu64*)(P.hsum + (size_t)d3 * 3 * RVM_HEDGE_STRIDE + hi[d3]);
+                            auto ld = [&](size_t o) {
+                                return __longlong_as_double((long long)__hip_atomic_load(es + o, __ATOMIC_RELAXED,
+                                                                                         __HIP_MEMORY_SCOPE_AGENT));
+                            };
+                            fl[d3] = pass_eval(q[d3], 2, ld(0), ld(RVM_HEDGE_STRIDE), d2, (int)ld(2 * RVM_HEDGE_STRIDE));
+                        }
+                        int stw = RVM_STATUS_OK, ncut = 0;
+                        double lp = 0.0;
+                        const bool dn = live ? decide(q[0], q[1], 2, stw, lp, ncut) : true;
+                        if (ballot(live && !dn) == 0) {
+                            took = true;
+                            if (live) {
+                                if (o0) dir_store(0, q[0], fl[0]);
+                                if (o1) dir_store(1, q[1], fl[1]);
+                                if (ncut)
+                                    __hip_atomic_fetch_add(P.counters + 4, (unsigned long long)ncut, __ATOMIC_RELAXED,
+                                                           __HIP_MEMORY_SCOPE_AGENT);
+                                live = false;
+                                s_live[lane] = 0;
+                                s_stw[lane] = stw;
+                                s_lpw[lane] = stw == RVM_STATUS_OK ? lp : -INFINITY;
+                            }
+                            rf_last = 2;
+                        }
+                    }
+                    if (lane == 0) {
+                        const unsigned long long nd = __builtin_popcountll(m0) + __builtin_popcountll(m1);
+                        if (took) __hip_atomic_fetch_add(P.counters + 3, nd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_fetch_add((gu64*)P.hw + RVM_HW_STATS + (took ? 1 : 2), nd, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                    if (took) m0 = m1 = 0;
+                }
                 if (lane == 0) {
                     s_mask[0] = m0;
                     s_mask[1] = m1;
@@ -1014,7 +1198,8 @@ __global__ __launch_bounds__(NW * 64) void refine_kernel(const DevPlan P, const 
         if (eager && threadIdx.x == 0)
             __hip_atomic_store(ef, (gen << 8) | 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #ifdef RVM_PROFILE
-        if (t == (int)blockIdx.x && lane == 0 && (size_t)blockIdx.x * 8 + wv < RVM_RPROF_MAX_WAVES) {
+        // (the records' upper half is the hedge blocks', hedge_kernel)
+        if (t == (int)blockIdx.x && lane == 0 && (size_t)blockIdx.x * 8 + wv < RVM_RPROF_MAX_WAVES / 2) {
             unsigned long long* o = rvm_rprof + ((size_t)blockIdx.x * 8 + wv) * RVM_RPROF_SLOTS;
             o[0] = prt_entry;
             o[1] = prt_loop0;
@@ -1038,6 +1223,7 @@ __global__ __launch_bounds__(NW * 64) void refine_kernel(const DevPlan P, const 
         }
 #endif
     }
+    leave();
 }
 
 // Eager halving passes (round 4): for a plain launch of 32..512 walkers (SMALA's centres, batched
@@ -1166,6 +1352,362 @@ static hipError_t launch_eager_t(const DevPlan& P, int W, const double* params, 
     return hipGetLastError();
 }
 
+// Hedged pass 2: at the bench's steady state about one walker slot in a 6144-slot
+// launch needs a second halving pass, and that launch waits for it -- one lone wave's chain of twice
+// pass 1's steps.  Which slots halve at all is not predictable, but the ones that go on to pass 2 are
+// nearly always among those with the quickest pericentre passage (scripts/probe/pass1_predictor_study.py,
+// profiles/r07_pass2_hedge_study.jsonl).
+// So a fused stretch launch whose likelihood grid leaves CUs idle runs pass 2 of the K = ngrp x WPB
+// slots that rank best by a (1 - e) / (1 + m)^(1/3), the smallest over the planets (the 2/3 power of
+// the pericentre passage time), on the plan's side stream beside the likelihood kernel: one block per
+// (group of WPB slots neighbouring in rank, direction), one wave per level, the block alone on its CU
+// (its dynamic LDS request is the CU's whole remainder).  Every block ranks the launch's slots itself
+// (keys in LDS, a radix select of the K-th, a stable compaction, a rank sort of the K: the same order in
+// every block), notes its slots' hedge indices (DevPlan::htab, hslot), and stores per walker-direction
+// the pass's RV per epoch, chi2, estimate and encounter flag write-through, then its completion word --
+// eager_kernel's layout and combiner.  The refinement kernel, when a group comes to pass 2, replays it
+// from these if they are complete for every open walker-direction of the group, and integrates it as
+// before if not: it never waits.  Its last block out sets the cancel word, which the hedge blocks
+// test before they start, every 64 steps and at every epoch; run_logl then joins the side stream and
+// advances the launch generation (gen_bump_kernel), as after an eager launch.
+template <int NP, bool D3>
+__global__ __launch_bounds__(256) void hedge_kernel(const DevPlan P, const int W, const double hill_factor,
+                                                    const StretchArgs sa, const int ngrp, const int skip) {
+    constexpr int L = LanesPerWalker<NP>::value;
+    constexpr int WPB = 64 / L;
+    constexpr int PR = D3 ? 7 : 5;
+    constexpr int R = PR * NP;
+    const int tid = threadIdx.x;
+    const int wv = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int slot = lane / L;
+    const int pl_idx = lane % L;
+    const int nl = P.n_levels;
+    const int g = blockIdx.x >> 1, dd = blockIdx.x & 1;
+    const DirSched& SR = dd ? P.bwd : P.fwd;
+    const int Er = SR.n_epochs;
+    extern __shared__ unsigned long long s_key[];  // [W] the slots' keys (the score's bits; all ones: not ranked)
+    __shared__ double s_rv[2][RVM_MAX_LEVELS][64];
+    __shared__ int s_enc[RVM_MAX_LEVELS][64];
+    __shared__ int s_cnt[2][256];
+    __shared__ unsigned long long s_ck[RVM_HEDGE_CAND];  // the candidates' keys and slots, in slot order
+    __shared__ int s_ci[RVM_HEDGE_CAND];
+    __shared__ int s_sel[64];  // this group's slots by rank
+    __shared__ int s_cancel[2];
+    __shared__ unsigned long long s_gen, s_pref;
+    __shared__ int s_need;
+#ifdef RVM_PROFILE
+    const unsigned long long prt_entry = __builtin_amdgcn_s_memrealtime();
+#endif
+    gu64* hw = (gu64*)P.hw;
+    if (tid == 0) s_gen = __hip_atomic_load(P.gen_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    const unsigned long long gen = s_gen;
+    const unsigned long long ctag = (gen << 8) | 1ull;
+    if (tid == 0) s_cancel[0] = __hip_atomic_load(hw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ctag;
+    __syncthreads();
+    if (s_cancel[0]) return;  // (before the slots are read)
+    const unsigned long long kbad = ~0ull;
+    for (int i = tid; i < RVM_HEDGE_CAND; i += 256) {
+        s_ck[i] = kbad;
+        s_ci[i] = 0;
+    }
+    // every slot's key from its proposal rows (the refinement prologue's own code)
+    for (int i = tid; i < W; i += 256) {
+        int kind = 0, wk = i, jst = 0, jp = 0;
+        double zst = 0.0, zp = 0.0;
+        stretch_slot(sa, i, kind, wk, zst, jst, zp, jp);
+        double sc = INFINITY;
+        bool ok = true;
+#pragma unroll
+        for (int p = 0; p < NP; p++) {
+            const double m = walker_param(true, nullptr, W, wk, sa, PR * p + 0, zst, jst, kind, zp, jp);
+            const double a = walker_param(true, nullptr, W, wk, sa, PR * p + 1, zst, jst, kind, zp, jp);
+            const double h = walker_param(true, nullptr, W, wk, sa, PR * p + 2, zst, jst, kind, zp, jp);
+            const double k = walker_param(true, nullptr, W, wk, sa, PR * p + 3, zst, jst, kind, zp, jp);
+            const double e = sqrt(h * h + k * k);
+            // (walker_setup's prior bounds: a slot outside them is never refined)
+            ok = ok && a > 0.02 && m > 5e-6 && e < 1.0;
+            sc = fmin(sc, a * (1.0 - e) / cbrt(1.0 + m));
+        }
+        ok = ok && isfinite(sc) && sc > 0.0;
+        s_key[i] = ok ? (unsigned long long)__double_as_longlong(sc) : kbad;
+    }
+    // four bins per lane of wave 0: the exclusive prefix sums of c[0..255] in place
+    auto scan256 = [&](int* c) {
+        const int c0 = c[4 * lane], c1 = c[4 * lane + 1], c2 = c[4 * lane + 2], c3 = c[4 * lane + 3];
+        int inc = c0 + c1 + c2 + c3;
+        for (int d = 1; d < 64; d <<= 1) {
+            const int v = __shfl_up(inc, d, 64);
+            if (lane >= d) inc += v;
+        }
+        const int ex = inc - (c0 + c1 + c2 + c3);
+        c[4 * lane] = ex;
+        c[4 * lane + 1] = ex + c0;
+        c[4 * lane + 2] = ex + c0 + c1;
+        c[4 * lane + 3] = ex + c0 + c1 + c2;
+    };
+    // the key of rank kq (1-based) among the W: a radix select, eight bits a round from the top
+    const int want = skip + ngrp * WPB;
+    const int kq = want < W ? want : W;
+    if (tid == 0) {
+        s_pref = 0;
+        s_need = kq;
+    }
+    for (int rd = 7; rd >= 0; rd--) {
+        const int sh = 8 * rd;
+        s_cnt[0][tid] = 0;
+        __syncthreads();
+        const unsigned long long pref = s_pref;
+        const unsigned long long hi = rd == 7 ? 0ull : (~0ull << (sh + 8));
+        for (int i = tid; i < W; i += 256) {
+            const unsigned long long key = s_key[i];
+            if ((key & hi) == pref) atomicAdd(&s_cnt[0][(int)((key >> sh) & 255)], 1);
+        }
+        __syncthreads();
+        if (wv == 0) {
+            const int need = s_need;
+            const int c0 = s_cnt[0][4 * lane], c1 = s_cnt[0][4 * lane + 1], c2 = s_cnt[0][4 * lane + 2],
+                      c3 = s_cnt[0][4 * lane + 3];
+            int inc = c0 + c1 + c2 + c3;
+            for (int d = 1; d < 64; d <<= 1) {
+                const int v = __shfl_up(inc, d, 64);
+                if (lane >= d) inc += v;
+            }
+            int ex = inc - (c0 + c1 + c2 + c3);
+            if (ex < need && need <= inc) {  // (one lane: the counts sum to at least `need`)
+                int b = 0;
+                if (need > ex + c0) {
+                    ex += c0;
+                    b = 1;
+                    if (need > ex + c1) {
+                        ex += c1;
+                        b = 2;
+                        if (need > ex + c2) {
+                            ex += c2;
+                            b = 3;
+                        }
+                    }
+                }
+                s_pref = pref | ((unsigned long long)(4 * lane + b) << sh);
+                s_need = need - ex;
+            }
+        }
+        __syncthreads();
+    }
+    // the candidates in slot order: every key below the kq-th, and the first of its equals (none of the
+    // unranked); a thread's slots are consecutive, its offsets the threads' counts' prefix sums
+    const unsigned long long kth = s_pref;
+    const int ntie = kth == kbad ? 0 : s_need;  // equals taken
+    const int nless = kq - s_need;
+    const int nsel = nless + ntie;
+    const int per = (W + 255) / 256;
+    const int i0 = tid * per < W ? tid * per : W, i1 = i0 + per < W ? i0 + per : W;
+    {
+        int a = 0, b = 0;
+        for (int i = i0; i < i1; i++) {
+            const unsigned long long key = s_key[i];
+            a += key < kth ? 1 : 0;
+            b += key == kth ? 1 : 0;
+        }
+        s_cnt[0][tid] = a;
+        s_cnt[1][tid] = b;
+    }
+    __syncthreads();
+    if (wv == 0) {
+        scan256(s_cnt[0]);
+        scan256(s_cnt[1]);
+    }
+    __syncthreads();
+    {
+        int a = s_cnt[0][tid], b = s_cnt[1][tid];
+        for (int i = i0; i < i1; i++) {
+            const unsigned long long key = s_key[i];
+            int pos = -1;
+            if (key < kth) {
+                pos = a++;
+            } else if (key == kth) {
+                if (b < ntie) pos = nless + b;
+                b++;
+            }
+            if (pos >= 0 && pos < RVM_HEDGE_CAND) {
+                s_ck[pos] = key;
+                s_ci[pos] = i;
+            }
+        }
+    }
+    __syncthreads();
+    // their ranks (by key, then slot); this group's are skip + g WPB .. + WPB
+    const int r0 = skip + g * WPB;
+    const int cnt = nsel - r0 < WPB ? nsel - r0 : WPB;
+    if (cnt <= 0) return;
+    for (int c = tid; c < nsel; c += 256) {
+        const unsigned long long key = s_ck[c];
+        int rk = 0;
+        for (int o = 0; o < nsel; o++) rk += (s_ck[o] < key || (s_ck[o] == key && o < c)) ? 1 : 0;
+        if (rk >= r0 && rk < r0 + WPB) s_sel[rk - r0] = s_ci[c];
+    }
+    __syncthreads();
+    // the slots' hedge indices (both directions' blocks store the same), and the slot at each index
+    if (wv == 0 && lane < cnt) {
+        const int hx = g * WPB + lane;
+        __hip_atomic_store((gu64*)P.htab + s_sel[lane], (gen << 16) | (unsigned long long)hx, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store((gu64*)P.hslot + (size_t)dd * RVM_HEDGE_STRIDE + hx,
+                           (gen << 16) | (unsigned long long)s_sel[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (tid == 0 && dd == 0)
+        __hip_atomic_fetch_add(hw + RVM_HW_STATS, (unsigned long long)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // pass 2 of the group's slots in this direction: eager_kernel's, with the slots' proposal rows
+    const int wo = s_sel[slot < cnt ? slot : 0];  // (lanes past the last slot repeat the group's first)
+    int kind = 0, wk = wo, jst = 0, jp = 0;
+    double zst = 0.0, zp = 0.0;
+    stretch_slot(sa, wo, kind, wk, zst, jst, zp, jp);
+    double rowv[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) rowv[r] = walker_param(true, nullptr, W, wk, sa, r, zst, jst, kind, zp, jp);
+    Lane<NP> s;
+    int status = RVM_STATUS_OK;
+    double e2w;
+    walker_setup<NP, D3, L>(rowv, pl_idx, hill_factor, s, status, e2w);
+    int k = wv < nl ? wv : -1;
+    k = __builtin_amdgcn_readfirstlane(k);
+    const int k_u = k < 0 ? 0 : k;
+    const bool work = k >= 0;
+    KickPrep<NP> kq0{};
+    if (work && Er > 0) kq0 = kick_prep<NP, L, D3>(s, 1.875);
+    constexpr int rf = 2;
+    const int m_r = P.mult[k_u] << rf;
+    const int nt_r = P.nt[k_u];
+    const bool late = P.late_mult > 0 && m_r >= P.late_mult;  // (the late vote: the same bits)
+    const double sc = ldexp(P.inv_mult[k_u], -rf);
+    const bool cmb = work && k == 0 && lane < cnt;
+    const int hx = g * WPB + (cmb ? lane : 0);
+    gu64* rvo = (gu64*)(P.hrv + (size_t)dd * P.lvx_emax * RVM_HEDGE_STRIDE + hx);
+    double c2 = 0.0, e2 = 0.0;
+    bool cancelled = false;
+#ifdef RVM_PROFILE
+    const unsigned long long prt_loop0 = __builtin_amdgcn_s_memrealtime();
+#endif
+    for (int e = 0; e < Er; e++) {
+        const int ns = __builtin_amdgcn_readfirstlane(work ? SR.seg_n[e] * m_r : 0);
+        // (a cancel lands within 64 steps: a wave it stops part-way holds a partial state, which the
+        // block discards -- the word stays set, and wave 0 reads it again before anything is published)
+        if (ns > 0)
+            (void)segment_gated_c<D3, NP, L, RVM_REFINE_GUESS>(s, kq0, SR.seg_h1[e] * sc, ns, nt_r, hw, nullptr, ctag, late);
+        if (work) {
+            const double v0 = star_vx<NP, L>(s);
+            if (pl_idx == 0) s_rv[e & 1][k_u][slot] = v0;
+        }
+        if (wv == 0 && lane == 0)
+            s_cancel[e & 1] = __hip_atomic_load(hw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ctag;
+        __syncthreads();
+        if (s_cancel[e & 1]) {
+            cancelled = true;
+            break;
+        }
+        if (cmb) {  // (the refinement kernel's combiner, expression for expression)
+            double rvx = 0.0, rv3 = 0.0;
+            for (int q = 0; q < nl; q++) rvx += P.lw[q] * s_rv[e & 1][q][lane];
+            for (int q = 1; q < nl; q++) rv3 += P.lw3[q] * s_rv[e & 1][q][lane];
+            const double ob = SR.obs_rv[e], s2 = SR.obs_s2[e];
+            const double r = rvx - ob;
+            c2 += (r * r) / s2;
+            e2 += fabs((rvx - rv3) * (r + (rv3 - ob))) / s2;
+            __hip_atomic_store(rvo + (size_t)e * RVM_HEDGE_STRIDE, (unsigned long long)__double_as_longlong(rvx),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+#ifdef RVM_PROFILE
+    if (lane == 0 && RVM_RPROF_MAX_WAVES / 2 + (size_t)blockIdx.x * 8 + wv < RVM_RPROF_MAX_WAVES) {
+        // (timing build: the hedge blocks' records after the refinement kernel's, [9] bit 29 set)
+        unsigned long long* o = rvm_rprof + (RVM_RPROF_MAX_WAVES / 2 + (size_t)blockIdx.x * 8 + wv) * RVM_RPROF_SLOTS;
+        o[0] = prt_entry;
+        o[1] = prt_loop0;
+        o[2] = __builtin_amdgcn_s_memrealtime();
+        o[3] = o[2];
+        o[9] = (unsigned long long)blockIdx.x | (1ull << 29) | ((unsigned long long)(cancelled ? 1 : 0) << 30);
+        o[10] = cancelled ? 0 : 1;
+        o[11] = (unsigned long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_REG_HW_ID
+    }
+#endif
+    if (cancelled) return;
+    if (work && pl_idx == 0) s_enc[k_u][slot] = (int)(((s.encm >> lane) & kick_enc_bits<NP>()) != 0);
+    __syncthreads();
+    if (wv == 0) {
+        // (a cancel that stopped another wave inside the last segment: seen here, after the barrier)
+        if (__builtin_amdgcn_readfirstlane((int)(__hip_atomic_load(hw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ctag)))
+            return;
+        if (cmb) {
+            int er = 0;
+            for (int q = 0; q < nl; q++) er |= s_enc[q][lane];
+            gu64* es = (gu64*)(P.hsum + (size_t)dd * 3 * RVM_HEDGE_STRIDE + hx);
+            auto bits = [](double v) { return (unsigned long long)__double_as_longlong(v); };
+            __hip_atomic_store(es, bits(c2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(es + RVM_HEDGE_STRIDE, bits(e2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(es + 2 * RVM_HEDGE_STRIDE, bits((double)er), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (lane == 0)
+            __hip_atomic_store(hw + 2 + 2 * g + dd, (gen << 8) | 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// the hedge kernel's dynamic LDS request on the current device: all the CU has left beside its static
+// LDS (no other block then shares its CU), with the attribute admitting it set once per device and
+// instantiation (prepare_refine_t, as refine_budget); 0: the kernel cannot run
+template <int NPV, bool D3V>
+static size_t hedge_budget() {
+    static size_t budget[64] = {};
+    static bool known[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    if (!known[dev]) {
+        const void* f = reinterpret_cast<const void*>(&hedge_kernel<NPV, D3V>);
+        hipFuncAttributes fa{};
+        size_t b = 0;
+        if (hipFuncGetAttributes(&fa, f) == hipSuccess && fa.sharedSizeBytes < (size_t)RVM_LDS_PER_CU) {
+            const size_t lim = (size_t)RVM_LDS_PER_CU - fa.sharedSizeBytes;
+            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lim) == hipSuccess) b = lim;
+        }
+        (void)hipGetLastError();
+        budget[dev] = b;
+        known[dev] = true;
+    }
+    return budget[dev];
+}
+
+// groups of walker slots a hedge of this launch may take: two CUs each of those the likelihood grid
+// (logl_blocks blocks, one per CU) leaves idle, the plan's cap, and no more than the slots fill
+template <int NPV, bool D3V>
+static int hedge_groups_t(const DevPlan& P, int W, int logl_blocks) {
+    constexpr int wpb = 64 / LanesPerWalker<NPV>::value;
+    if (P.hedge_groups <= 0 || P.hw == nullptr || P.rvp == nullptr || P.rmax < 2 || P.n_levels > 4 || W < 1 ||
+        W > RVM_HEDGE_MAX_W || W > P.rq_cap || (size_t)W * sizeof(unsigned long long) > hedge_budget<NPV, D3V>())
+        return 0;
+    const int idle = P.n_cu - logl_blocks;
+    int n = std::min(P.hedge_groups, idle / 2);
+    n = std::min(n, (W + wpb - 1) / wpb);
+    return n > 0 ? n : 0;
+}
+
+template <int NPV, bool D3V>
+static hipError_t launch_hedge_t(const DevPlan& P, int W, double hill_factor, const StretchArgs& sa, int ngrp,
+                                 hipStream_t st) {
+    constexpr int wpb = 64 / LanesPerWalker<NPV>::value;
+    // The best-ranked group of slots is left out where the launch has slots enough to rank beyond it: in
+    // the oracle study no pass-2 slot ranked better than 56 of 6144 (the most extreme proposals are cut or
+    // end ENCOUNTER first; ranks 33 .. 288 cover what 1 .. 256 do), and those near-parabolic slots' pass 2
+    // is the slowest -- with them the hedge kernel ran until it was cancelled, 1.26 ms median beside 1.26 ms
+    // of likelihood and refinement kernels, and the join waited for the cancel to land
+    const int skip = W >= 2 * (ngrp + 1) * wpb ? wpb : 0;
+    hedge_kernel<NPV, D3V><<<dim3(2 * ngrp), dim3(256), hedge_budget<NPV, D3V>(), st>>>(P, W, hill_factor, sa, ngrp, skip);
+    return hipGetLastError();
+}
+
 // Dynamic-LDS budget of the refinement kernel on the current device (the CU's 160 KB less its static
 // LDS), with the attribute admitting it set once per device and instantiation.  rvm_plan_create
 // calls it (prepare_refine) so a launch never changes function attributes -- launches stay
@@ -1194,7 +1736,7 @@ static size_t refine_budget() {
 
 template <int NPV, bool D3V>
 static hipError_t launch_refine_t(const DevPlan& P, int W, const double* params, double hill_factor, double* logl,
-                                  int32_t* status, double* rv_out, const StretchArgs& sa, int eager,
+                                  int32_t* status, double* rv_out, const StretchArgs& sa, int eager, int hedge,
                                   hipStream_t stream) {
     constexpr int wpb = 64 / LanesPerWalker<NPV>::value;
     const int emax = P.fwd.n_epochs > P.bwd.n_epochs ? P.fwd.n_epochs : P.bwd.n_epochs;
@@ -1215,10 +1757,10 @@ static hipError_t launch_refine_t(const DevPlan& P, int W, const double* params,
     nb &= ~1;
     if (w4)
         refine_kernel<NPV, D3V, 4><<<dim3(nb), dim3(256), smem, stream>>>(P, W, params, hill_factor, rv_out, logl, status,
-                                                                          sa, eager);
+                                                                          sa, eager, hedge);
     else
         refine_kernel<NPV, D3V, 8><<<dim3(nb), dim3(512), smem, stream>>>(P, W, params, hill_factor, rv_out, logl, status,
-                                                                          sa, eager);
+                                                                          sa, eager, hedge);
     return hipGetLastError();
 }
 
@@ -1228,6 +1770,7 @@ static hipError_t prepare_refine_t(const DevPlan& P) {
     const int emax = P.fwd.n_epochs > P.bwd.n_epochs ? P.fwd.n_epochs : P.bwd.n_epochs;
     const size_t smem = (size_t)emax * 8 * sizeof(double);
     const size_t b = std::min(refine_budget<NPV, D3V, 4>(), refine_budget<NPV, D3V, 8>());
+    if (P.hedge_groups > 0) (void)hedge_budget<NPV, D3V>();  // (the hedge kernel's LDS attribute, set here once)
     return smem <= b ? hipSuccess : hipErrorInvalidConfiguration;
 }
 
@@ -1235,8 +1778,11 @@ static hipError_t prepare_refine_t(const DevPlan& P) {
 // compiles them in parallel) export these
 #define RVM_REFINE_NP_API(N)                                                                                     \
     hipError_t launch_refine_np##N(const DevPlan& P, int W, const double* params, double hill_factor, double* logl, \
-                                   int32_t* status, double* rv_out, const StretchArgs& sa, int eager,            \
+                                   int32_t* status, double* rv_out, const StretchArgs& sa, int eager, int hedge, \
                                    hipStream_t stream);                                                          \
+    int hedge_groups_np##N(const DevPlan& P, int W, int logl_blocks);                                           \
+    hipError_t launch_hedge_np##N(const DevPlan& P, int W, double hill_factor, const StretchArgs& sa, int ngrp, \
+                                  hipStream_t stream);                                                           \
     hipError_t launch_eager_np##N(const DevPlan& P, int W, const double* params, double hill_factor,            \
                                   hipStream_t stream);                                                           \
     hipError_t prepare_refine_np##N(const DevPlan& P);

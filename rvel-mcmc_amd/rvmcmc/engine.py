@@ -222,6 +222,16 @@ class LoglPlan:
                 tot[k] += v
         return f
 
+    def hedge_stats(self, reset=False, stream=None) -> dict:
+        """rvm_plan_hedge_stats (synchronises the stream): walker slots whose second halving pass ran
+        beside the likelihood kernel, pass-2 walker-directions the refinement kernel replayed from
+        those, and pass-2 walker-directions of such launches it integrated itself.  Timing-dependent,
+        hence not part of faults()."""
+        h, r, m = C.c_int64(), C.c_int64(), C.c_int64()
+        _lib.check(self.lib.rvm_plan_hedge_stats(self._h, int(bool(reset)), C.byref(h), C.byref(r), C.byref(m),
+                                                 _lib.stream_handle(stream)), "rvm_plan_hedge_stats")
+        return dict(hedged=h.value, replayed=r.value, missed=m.value)
+
     def check_faults(self, what="plan", stream=None, group=None) -> dict:
         """Raise RvmError on hand-off timeouts, NONFINITE results, or (a plan that refines, resolve_max
         > 0) UNRESOLVED results since the last check: emcee raises on a NaN log-probability

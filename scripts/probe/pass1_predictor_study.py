@@ -9,6 +9,8 @@ pass2_study.py forms them): the slots whose walker needs halving pass 1 (oracle 
 stage >= 2 in a direction, not cut before it), and per score the rank of the worst such slot -- the
 K that would have caught them all.  Scores: tau = min over planets of P (1 - e)^1.5 (the quickest
 pericentre passage), max e, and the eccentricity-guard factor.
+The "hedge" score is the key the hedged pass 2 ranks by (rvm_refine_impl.h hedge_kernel): per iteration
+the ranks of the slots that go on to pass 2 and whether the best K = 128, 192, 256, 512 cover them.
 usage: pass1_predictor_study.py [iterations] -> JSON lines."""
 import json
 import os
@@ -36,7 +38,13 @@ def scores(P):
         tau = per * np.clip(1.0 - e, 1e-6, None) ** 1.5
         # closest possible approach of the pair: a_o (1 - e_o) - a_i (1 + e_i), relative to a_i
         gap = (a[:, 1] * (1 - e[:, 1]) - a[:, 0] * (1 + e[:, 0])) / a[:, 0]
+    # the hedge kernel's key (rvm_refine_impl.h hedge_kernel): a (1 - e) / (1 + m)^(1/3), the smallest over
+    # the planets -- tau^(2/3), the same order as inv_tau; slots outside the prior bounds are not ranked
+    with np.errstate(invalid="ignore", divide="ignore"):
+        key = np.min(a * (1.0 - e) / np.cbrt(1.0 + m), axis=1)
+    ok = np.all((a > 0.02) & (m > 5e-6) & (e < 1.0), axis=1) & np.isfinite(key) & (key > 0)
     return {"inv_tau": 1.0 / np.min(tau, axis=1), "max_e": np.max(e, axis=1), "neg_gap": -gap,
+            "hedge": np.where(ok, -key, -np.inf),
             "inv_tau_x_gap": (1.0 / np.min(tau, axis=1)) * np.exp(-np.clip(gap, -5, 5) * 4.0)}
 
 
@@ -100,6 +108,14 @@ def main():
             out[f"K_all_halving_{name}"] = int(rank[halving].max()) + 1 if halving.any() else 0
             out[f"K_all_pass2_{name}"] = int(rank[deep].max()) + 1 if deep.any() else 0
             out[f"halving_in_top512_{name}"] = int((rank[halving] < 512).sum())
+            if name == "hedge":
+                # the hedged pass 2: the pass-2 slots' ranks (1-based), and whether the
+                # K best-ranked slots cover all of them -- from rank 1, and with the first 32 left out
+                out["pass2_ranks_hedge"] = sorted(int(r) + 1 for r in rank[deep])
+                for K in (128, 192, 256, 512):
+                    out[f"pass2_covered_K{K}"] = bool(deep.any() and rank[deep].max() < K)
+                    out[f"pass2_covered_K{K}_skip32"] = bool(deep.any() and rank[deep].min() >= 32 and
+                                                             rank[deep].max() < K + 32)
         print(json.dumps(out), flush=True)
         pos[0] = np.where(acc0[:, None], q0, pos[0])
         lnp[0] = np.where(acc0, l0, lnp[0])

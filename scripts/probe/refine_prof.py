@@ -53,9 +53,22 @@ def main():
         assert lib.rvm_rprof_copy(buf.ctypes.data, buf.nbytes) == 0
         b = buf.reshape(MAXW, SLOTS).astype(np.int64)
         b = b[b[:, 3] != 0]
+        # the hedged pass 2's blocks ([9] bit 29; rvm_refine_impl.h hedge_kernel) apart: they start beside
+        # the likelihood kernel, before the refinement kernel's waves
+        hb = b[((b[:, 9] >> 29) & 1) == 1]
+        b = b[((b[:, 9] >> 29) & 1) == 0]
         if not len(b):
             continue
         t_launch0 = b[:, 0].min()
+        hedge = None
+        if len(hb):
+            # against the refinement kernel's first wave (negative: before it), in us; blocks that ran to
+            # their end against those a cancel stopped ([9] bit 30)
+            hedge = {"blocks": int(len(set((hb[:, 9] & 0xFFFF).tolist()))),
+                     "start_us": [float(hb[:, 0].min() - t_launch0) / 100.0, float(hb[:, 0].max() - t_launch0) / 100.0],
+                     "select_us_median": float(np.median(hb[:, 1] - hb[:, 0]) / 100.0),
+                     "end_us": [float(hb[:, 2].min() - t_launch0) / 100.0, float(hb[:, 2].max() - t_launch0) / 100.0],
+                     "cancelled_waves": int(((hb[:, 9] >> 30) & 1).sum()), "waves": int(len(hb))}
         span = (b[:, 3].max() - t_launch0) / 100.0  # us
         busy = b[b[:, 6] > 0]
         i = int(np.argmax(b[:, 3]))
@@ -63,6 +76,7 @@ def main():
         us = lambda x: float(x) / 100.0  # noqa: E731
         clk = float(w[7] + w[8]) / max(1.0, (w[2] - w[0]) * 10.0)  # cycles per ns = GHz
         out = {"it": it, "wall_ms": 1e3 * wall, "span_us": span, "waves": int(len(b)), "busy_waves": int(len(busy)),
+               "hedge": hedge,
                "tasks": int(len(set((b[:, 9] & 0xFFFF).tolist()))),
                "slowest": {"entry_us": us(w[0] - t_launch0), "prologue_us": us(w[1] - w[0]),
                            "loop_us": us(w[2] - w[1]), "tail_us": us(w[3] - w[2]),

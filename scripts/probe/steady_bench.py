@@ -48,7 +48,10 @@ def run(resolve_tol, levels=(4, 5, 6, 7), resolve_max=None, iters=int(os.environ
                 faults_warm=f0, logl_kernel_ms=float(np.mean(km)) if len(km) else None,
                 refine_kernel_ms=float(np.mean(kr)) if len(kr) else None,
                 refine_kernel_ms_quantiles=[float(v) for v in np.quantile(kr, [0, .25, .5, .75, 1])] if len(kr) else None,
-                lib=os.environ.get("RVM_LIB_PATH", "default"))
+                lib=os.environ.get("RVM_LIB_PATH", "default"),
+                # (the hedged pass 2's statistics over warm-up and timed iterations; a library without it: None)
+                hedge=ens.plan.hedge_stats() if hasattr(ens.plan, "hedge_stats") else None,
+                hedge_env={k: os.environ.get(k) for k in ("RVM_HEDGE", "RVM_HEDGE_GROUPS", "RVM_REFINE_TEAMS")})
 
 
 if __name__ == "__main__":
