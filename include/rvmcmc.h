@@ -307,6 +307,35 @@ int rvm_pt_swap(int32_t n_params, int32_t n_temps, int32_t n_half, const double*
                 double* lnp0, double* lnp1, uint64_t seed, uint64_t iteration, const double* draws,
                 int32_t* swapped, void* stream);
 
+/* The ladder's dynamics and the per-temperature log-likelihood moments, after an exchange sweep
+ * (ptemcee sampler.py Sampler._get_ladder_adjustment, called from Sampler.sample once per iteration;
+ * emcee 2.2.1 ptsampler.py PTSampler.sample stores the per-temperature lnlikelihood that
+ * PTSampler.thermodynamic_integration_log_evidence averages).  Two launches on `stream`, no
+ * floating-point atomics, the same bits from run to run:
+ *   total[p] = sum_w swapped[p][w] (int64) ; count[p] = total[p] - swap_totals_prev[p] ;
+ *   swap_totals_prev[p] = total[p] ; ratios_out[p] = (double)count[p] / (double)W        p < n_temps-1
+ *   lnp_moments[t][0] += sum_w lnp[t][w] ; lnp_moments[t][1] += sum_w lnp[t][w]^2   (when not null;
+ *     w in index order, half 0 first: per-thread strided partials of 256 threads, then a tree)
+ *   and, with n_temps >= 3 (both end temperatures stay fixed: beta = 0 is refused, so the hottest
+ *   temperature is finite), every expression left to right, A = ratios_out:
+ *     dS[i] = kappa * (A[i] - A[i+1]) ; dT[i] = (1/betas[i+1] - 1/betas[i]) * exp(dS[i])   i = 0 .. n_temps-3
+ *     acc = 1/betas[0] ; acc = acc + dT[i] ; new[i+1] = 1 / acc
+ *   If every dS is 0 (kappa = 0, equal ratios) betas stay bit for bit.  Else if any new beta is not
+ *   finite or the new ladder is not strictly decreasing down to the fixed betas[n_temps-1] (the
+ *   interior can overshoot it), betas stay and *n_refused += 1.  Else betas[1 .. n_temps-2] = new.
+ * swapped: rvm_pt_swap's int32 [n_temps-1][W]; lnp0, lnp1: the halves' lnp [n_temps * n_half];
+ * betas [n_temps] in/out; swap_totals_prev int64 [n_temps-1] in/out; ratios_out [n_temps-1];
+ * n_refused int64 [1] in/out; lnp_moments [n_temps][2] in/out, may be null (the moment rows are then
+ * not launched); workspace: 3 n_temps - 1 words of 8 bytes that carry the totals and this call's
+ * moments from the first launch to the second (contents unspecified before and after).  All device
+ * arrays.  Argument errors (n_temps or n_half < 1; n_temps * W beyond int32; kappa negative or not
+ * finite; a null pointer other than lnp_moments) return < 0 before any HIP call and name the argument
+ * in rvm_last_error.  n_temps = 1 returns 0 without a launch (the array arguments are not read). */
+int rvm_pt_ladder_update(int32_t n_temps, int32_t n_half, const int32_t* swapped, const double* lnp0,
+                         const double* lnp1, double kappa, double* betas, int64_t* swap_totals_prev,
+                         double* ratios_out, int64_t* n_refused, double* lnp_moments, void* workspace,
+                         void* stream);
+
 /* Gaussian random-walk Metropolis-Hastings (mcmc.py:89-121), n_chains independent chains:
  * propose: q = x + step_size * scales[p] * N(0,1)        draws layout: [n_params][n_chains]
  * accept : exp(lnp_new - lnp_old) > u -> x <- q, lnp <- lnp_new   draws layout: [n_chains] */

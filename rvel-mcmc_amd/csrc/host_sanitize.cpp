@@ -74,6 +74,16 @@ int main() {
            "pt swap int32 overflow");
     expect(rvm_pt_swap(10, 1, 4, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr) == 0,
            "pt swap of one temperature");
+    int64_t l1 = 0;
+    expect(rvm_pt_ladder_update(3, 1, &i1, &d1, &d1, -1.0, &d1, &l1, &d1, &l1, nullptr, &d1, nullptr) < 0,
+           "pt ladder kappa < 0");
+    expect(rvm_pt_ladder_update(3, 1, &i1, &d1, &d1, 0.5, &d1, &l1, &d1, &l1, nullptr, nullptr, nullptr) < 0,
+           "pt ladder null workspace");
+    expect(rvm_pt_ladder_update(1 << 16, 1 << 15, &i1, &d1, &d1, 0.5, &d1, &l1, &d1, &l1, nullptr, &d1, nullptr) < 0,
+           "pt ladder int32 overflow");
+    expect(rvm_pt_ladder_update(1, 4, nullptr, nullptr, nullptr, 0.5, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                nullptr, nullptr) == 0,
+           "pt ladder of one temperature");
     expect(rvm_mh_accept(0, 1, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr) < 0, "mh bad");
     expect(rvm_fd_params(10, 1, nullptr, 1e-6, nullptr, nullptr, nullptr) < 0, "fd bad");
     const int32_t rows[2] = {0, 0};

@@ -60,6 +60,7 @@ hipError_t launch_pt_stretch_accept(int P, int T, int Wh, const double* betas, d
 hipError_t launch_pt_swap(int P, int T, int Wh, const double* betas, double* x0, double* x1, double* lnp0,
                           double* lnp1, uint64_t seed, uint64_t it, const double* draws, int32_t* swapped,
                           hipStream_t st);
+hipError_t launch_pt_ladder_update(const PtLadderArgs& g, hipStream_t st);
 hipError_t launch_fd_params(int P, int n, const double* x, double rel, const double* fl, double* out, hipStream_t st);
 hipError_t launch_smala_derive(int P, int C, int E, const double* x, double rel, const double* fl,
                                const double* lp_st, const int32_t* st_st, const double* rv, const double* w,
@@ -1054,6 +1055,39 @@ int rvm_pt_swap(int32_t n_params, int32_t n_temps, int32_t n_half, const double*
     hipError_t e = rvm::launch_pt_swap(n_params, n_temps, n_half, betas, x0, x1, lnp0, lnp1, seed, iteration, draws,
                                        swapped, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "rvm_pt_swap");
+}
+
+int rvm_pt_ladder_update(int32_t n_temps, int32_t n_half, const int32_t* swapped, const double* lnp0,
+                         const double* lnp1, double kappa, double* betas, int64_t* swap_totals_prev,
+                         double* ratios_out, int64_t* n_refused, double* lnp_moments, void* workspace,
+                         void* stream) {
+    if (const char* m = pt_bad_shape(1, n_temps, n_half, 2 * (int64_t)n_half))
+        return fail(-1, std::string("rvm_pt_ladder_update: ") + m);
+    if (!std::isfinite(kappa) || kappa < 0.0) return fail(-1, "rvm_pt_ladder_update: kappa must be finite and >= 0");
+    if (n_temps == 1) return 0;  // one temperature has no ladder: nothing to launch
+    if (!swapped) return fail(-1, "rvm_pt_ladder_update: null swapped");
+    if (!lnp0 || !lnp1) return fail(-1, "rvm_pt_ladder_update: null lnp0 or lnp1");
+    if (!betas) return fail(-1, "rvm_pt_ladder_update: null betas");
+    if (!swap_totals_prev) return fail(-1, "rvm_pt_ladder_update: null swap_totals_prev");
+    if (!ratios_out) return fail(-1, "rvm_pt_ladder_update: null ratios_out");
+    if (!n_refused) return fail(-1, "rvm_pt_ladder_update: null n_refused");
+    if (!workspace) return fail(-1, "rvm_pt_ladder_update: null workspace");
+    rvm::PtLadderArgs g;
+    g.T = n_temps;
+    g.Wh = n_half;
+    g.swapped = swapped;
+    g.lnp0 = lnp0;
+    g.lnp1 = lnp1;
+    g.kappa = kappa;
+    g.betas = betas;
+    g.totals_prev = swap_totals_prev;
+    g.ratios = ratios_out;
+    g.n_refused = n_refused;
+    g.moments = lnp_moments;
+    g.ws_totals = (int64_t*)workspace;
+    g.ws_moments = (double*)workspace + (n_temps - 1);
+    hipError_t e = rvm::launch_pt_ladder_update(g, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rvm_pt_ladder_update");
 }
 
 int rvm_mh_propose(int32_t n_params, int32_t n_chains, int64_t chain_begin, const double* x, const double* scales,

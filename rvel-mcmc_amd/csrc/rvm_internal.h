@@ -299,6 +299,22 @@ struct IterEndArgs {
     int32_t* status_new_out;    // [n] (nullable)
 };
 
+// rvm_pt_ladder_update by value (rvm_tempering.hip: pt_ladder_stats_kernel, pt_ladder_adapt_kernel)
+struct PtLadderArgs {
+    int32_t T, Wh;              // temperatures, walkers per half of one temperature (W = 2 Wh)
+    const int32_t* swapped;     // [T-1][W] cumulative exchange counters of rvm_pt_swap
+    const double* lnp0;         // [T * Wh] half 0's untempered log-probabilities
+    const double* lnp1;         // [T * Wh] half 1's
+    double kappa;               // the dynamics' gain of this update (>= 0)
+    double* betas;              // [T] in/out
+    int64_t* totals_prev;       // [T-1] in/out: the counter rows' totals at the previous update
+    double* ratios;             // [T-1] out: exchanges per walker since the previous update
+    int64_t* n_refused;         // [1] in/out
+    double* moments;            // [T][2] in/out accumulators of sum lnp, sum lnp^2 (nullable)
+    int64_t* ws_totals;         // workspace words [0, T-1): this update's counter totals
+    double* ws_moments;         // workspace words [T-1, 3T-1): this update's [T][2] moments
+};
+
 // rvm_smala_cache by value as a kernel argument (same layout)
 struct SmalaCache {
     double* lp;

@@ -104,6 +104,112 @@ __global__ void pt_swap_kernel(int P, int T, int Wh, const double* __restrict__ 
     }
 }
 
+// ---- the ladder's statistics and dynamics (rvm_pt_ladder_update) -----------------------------------
+// One block of 256 threads per row.  Rows 0 .. T-2: the int64 total of the cumulative counter row
+// swapped[p][0..W) (integer sums do not depend on the order).  Rows T-1 .. 2T-2 (launched only when
+// the moments are asked for): sum lnp and sum lnp^2 over temperature t's W walkers in the index
+// order j = 0 .. W-1 (half 0's columns t Wh .. t Wh + Wh - 1, then half 1's): thread i adds j = i,
+// i + 256, ... in that order, then an LDS tree over the 256 slots -- a fixed order, no atomics, the
+// same bits from run to run.
+__global__ void __launch_bounds__(256) pt_ladder_stats_kernel(PtLadderArgs g) {
+    __shared__ int64_t sn[256];
+    __shared__ double s1[256], s2[256];
+    const int tid = (int)threadIdx.x, row = (int)blockIdx.x;  // (the branches below are block-uniform)
+    const int Wh = g.Wh, W = 2 * g.Wh;
+    if (row < g.T - 1) {
+        const int32_t* r = g.swapped + (size_t)row * W;
+        int64_t part = 0;
+        for (int w = tid; w < W; w += 256) part += r[w];
+        sn[tid] = part;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (tid < s) sn[tid] += sn[tid + s];
+            __syncthreads();
+        }
+        if (tid == 0) g.ws_totals[row] = sn[0];
+        return;
+    }
+    const int t = row - (g.T - 1);
+    if (t >= g.T) return;
+    const double* l0 = g.lnp0 + (size_t)t * Wh;
+    const double* l1 = g.lnp1 + (size_t)t * Wh;
+    double a = 0.0, b = 0.0;
+    for (int j = tid; j < W; j += 256) {
+        const double v = j < Wh ? l0[j] : l1[j - Wh];
+        a = a + v;
+        b = b + v * v;
+    }
+    s1[tid] = a;
+    s2[tid] = b;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) {
+            s1[tid] = s1[tid] + s1[tid + s];
+            s2[tid] = s2[tid] + s2[tid + s];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        g.ws_moments[2 * t] = s1[0];
+        g.ws_moments[2 * t + 1] = s2[0];
+    }
+}
+
+// The dynamics of Vousden, Farr & Mandel 2016 with both end temperatures fixed, every expression
+// left to right:
+//   dS[i] = kappa (A[i] - A[i+1]) ; dT[i] = (1/beta[i+1] - 1/beta[i]) exp(dS[i]) ;
+//   acc = 1/beta[0] ; acc = acc + dT[i] ; new[i+1] = 1 / acc                       i = 0 .. T-3
+// With store = false only the verdict: ok (every new beta finite, the ladder still strictly
+// decreasing down to the fixed beta[T-1]) and driven (some dS != 0).  The second pass repeats the
+// same operations on the same inputs (beta[i+1] is read before it is overwritten), so it stores
+// exactly what the first one judged, with no scratch array and no bound on T.
+__device__ static void pt_ladder_pass(const PtLadderArgs& g, bool store, bool& ok, bool& driven) {
+    const int T = g.T;
+    ok = true;
+    driven = false;
+    double tm = 1.0 / g.betas[0];
+    double acc = tm, prev = g.betas[0];
+    for (int i = 0; i <= T - 3; i++) {
+        const double dS = g.kappa * (g.ratios[i] - g.ratios[i + 1]);
+        if (dS != 0.0) driven = true;
+        const double tn = 1.0 / g.betas[i + 1];
+        const double dT = (tn - tm) * exp(dS);
+        acc = acc + dT;
+        const double nb = 1.0 / acc;
+        if (!isfinite(nb) || !(prev > nb)) ok = false;
+        if (store) g.betas[i + 1] = nb;
+        prev = nb;
+        tm = tn;
+    }
+    if (!(prev > g.betas[T - 1])) ok = false;  // the interior may not pass the fixed hottest temperature
+}
+
+// One block, one thread: at T <= 64 the update is serial and tiny.
+__global__ void pt_ladder_adapt_kernel(PtLadderArgs g) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const int T = g.T;
+    const double W = (double)(2 * g.Wh);
+    for (int p = 0; p < T - 1; p++) {
+        const int64_t total = g.ws_totals[p];
+        const int64_t count = total - g.totals_prev[p];
+        g.totals_prev[p] = total;
+        g.ratios[p] = (double)count / W;
+    }
+    if (g.moments)
+        for (int i = 0; i < 2 * T; i++) g.moments[i] = g.moments[i] + g.ws_moments[i];
+    if (T < 3) return;  // no interior temperature
+    bool ok, driven;
+    pt_ladder_pass(g, false, ok, driven);
+    // no drive (kappa = 0, or equal ratios): the ladder stays bit for bit (1 / (1 / beta) need not
+    // give beta back), and that is no refusal
+    if (!driven) return;
+    if (!ok) {
+        *g.n_refused += 1;
+        return;
+    }
+    pt_ladder_pass(g, true, ok, driven);
+}
+
 static inline dim3 grid1(int n) { return dim3((unsigned)(((int64_t)n + 255) / 256)); }
 
 hipError_t launch_pt_stretch_propose(int P, int T, int Wh, const double* x, const double* c, double a, uint64_t seed,
@@ -123,6 +229,14 @@ hipError_t launch_pt_swap(int P, int T, int Wh, const double* betas, double* x0,
                           double* lnp1, uint64_t seed, uint64_t it, const double* draws, int32_t* swapped,
                           hipStream_t st) {
     pt_swap_kernel<<<grid1(2 * Wh), 256, 0, st>>>(P, T, Wh, betas, x0, x1, lnp0, lnp1, seed, it, draws, swapped);
+    return hipGetLastError();
+}
+hipError_t launch_pt_ladder_update(const PtLadderArgs& g, hipStream_t st) {
+    const unsigned rows = (unsigned)(g.T - 1) + (g.moments ? (unsigned)g.T : 0u);
+    pt_ladder_stats_kernel<<<dim3(rows), 256, 0, st>>>(g);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    pt_ladder_adapt_kernel<<<dim3(1), 64, 0, st>>>(g);
     return hipGetLastError();
 }
 

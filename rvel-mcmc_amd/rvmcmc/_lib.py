@@ -112,6 +112,8 @@ SIGNATURES = {
                                         C.c_uint64, C.c_uint32, _dp, _dp, _dp]),
     "rvm_pt_swap": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.c_uint64, C.c_uint64, _dp,
                               _dp, _dp]),
+    "rvm_pt_ladder_update": (C.c_int, [C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp,
+                                       _dp]),
     "rvm_stretch_half_step": (C.c_int, [C.c_void_p, C.POINTER(ParamMapC), C.c_int32, C.c_int32, C.c_int64, _dp, _dp,
                                         _dp, C.c_int32, _dp, C.c_double, C.c_uint64, C.c_uint64, C.c_uint32,
                                         C.c_double, _dp, _dp, _dp, _dp]),

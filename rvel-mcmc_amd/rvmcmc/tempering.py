@@ -21,6 +21,19 @@ draws keyed by (seed, iteration, stream, item) with item t * W + h * W/2 + k for
 streams -- at T = 1 exactly EnsembleSampler's global walker index, and PTSampler(1, W, ...) then
 reproduces EnsembleSampler's unfused path bit for bit -- and p * W + w on stream 7 for the swaps.
 
+With adapt=True the ladder follows the dynamics of Vousden, Farr & Mandel 2016 (ptemcee's default)
+after every exchange sweep, on the device (rvm_pt_ladder_update): with A_p the exchanges per walker
+of pair p since the previous update and kappa = (lag / (n + lag)) / adaptation_time at update n,
+
+    dS_i = kappa (A_i - A_i+1) ;  T_i+1 - T_i  <-  (T_i+1 - T_i) exp(dS_i)        (T = 1 / beta)
+
+with both end temperatures fixed (beta = 0 is refused, so the hottest one is finite): a pair that
+exchanges less than its hotter neighbour moves closer.  An update whose result is not a strictly
+decreasing finite ladder is refused and counted (ladder_refusals()).  The adaptation breaks detailed
+balance while it runs -- it dies away as lag / n -- so adapt during burn-in, then freeze_ladder().
+record_lnprob(True) then accumulates the per-temperature moments of lnp on the device;
+mean_lnprob() and log_evidence_ratio() (thermodynamic integration) read them.
+
 The sampler is unfused (propose / likelihood / accept launches): a ladder of T temperatures already
 puts T W/2 walkers into every likelihood launch, which is what the fused and speculative launches
 of EnsembleSampler were built to achieve for a single ensemble.  Single process only.
@@ -54,6 +67,13 @@ def default_betas(ntemps, dim):
     return np.array([r ** -t for t in range(ntemps)], dtype=np.float64)
 
 
+def _positive(v, name):
+    v = float(v)
+    if not (math.isfinite(v) and v > 0.0):
+        raise ValueError(f"{name} must be finite and > 0")
+    return v
+
+
 def check_betas(betas, ntemps):
     """The ladder as float64 [ntemps]: strictly decreasing, 0 < beta <= 1 (beta = 0 would sample the
     hard prior alone, which is improper in a and m)."""
@@ -71,9 +91,26 @@ def check_betas(betas, ntemps):
     return b
 
 
+def log_evidence_ratio(betas, mean_lnp):
+    """(estimate, coarse) of the integral of mean_lnp d(beta) from betas[-1] up to betas[0]: the
+    trapezoid rule over all temperatures, and over every second one (0, 2, 4, ..., and the hottest,
+    so that both cover the same range)."""
+    b, m = np.asarray(betas, dtype=np.float64), np.asarray(mean_lnp, dtype=np.float64)
+
+    def trapezoid(idx):
+        s = 0.0
+        for i, j in zip(idx[-2::-1], idx[:0:-1]):  # hottest interval first: (colder i, hotter j)
+            s = s + (b[i] - b[j]) * (0.5 * (m[i] + m[j]))
+        return float(s)
+
+    fine = list(range(len(b)))
+    coarse = fine[::2] if fine[-1] % 2 == 0 else fine[::2] + [fine[-1]]
+    return trapezoid(fine), trapezoid(coarse)
+
+
 class PTSampler:
     def __init__(self, ntemps, nwalkers, state, obs, betas=None, a=2.0, seed=0, device=None, hill_factor=None,
-                 swap_every=1):
+                 swap_every=1, adapt=False, adaptation_lag=10000, adaptation_time=100):
         # value checks first: nothing below them touches the device
         dim = state.Nvars
         ntemps, nwalkers = int(ntemps), int(nwalkers)
@@ -90,6 +127,9 @@ class PTSampler:
             raise ValueError("swap_every must be at least 1")
         if ntemps * nwalkers > 2 ** 31 - 1:
             raise ValueError("ntemps * nwalkers must fit a 32-bit index")
+        self.adaptation_lag = _positive(adaptation_lag, "adaptation_lag")
+        self.adaptation_time = _positive(adaptation_time, "adaptation_time")
+        self.adapt = bool(adapt)
         torch = _torch()
         if torch.distributed.is_available() and torch.distributed.is_initialized() \
                 and torch.distributed.get_world_size() > 1:
@@ -117,6 +157,16 @@ class PTSampler:
         self._status = torch.empty(self.n, **i32)
         self.naccepted = torch.zeros((2, self.n), **i32)              # [half][t * W/2 + k]
         self.nswapped = torch.zeros((max(ntemps - 1, 0), nwalkers), **i32)  # [pair][w]
+        # the ladder's dynamics and the lnp moments (rvm_pt_ladder_update)
+        i64 = dict(dtype=torch.int64, device=self.device)
+        self._swap_prev = torch.zeros(max(ntemps - 1, 0), **i64)  # the counter rows' totals at the last update
+        self._ratios = torch.zeros(max(ntemps - 1, 0), **f64)     # exchanges per walker since the one before
+        self._n_refused = torch.zeros(1, **i64)
+        self._moments = torch.zeros((ntemps, 2), **f64)           # [t]: sum lnp, sum lnp^2 while recording
+        self._work = torch.empty(3 * ntemps - 1, **f64)
+        self.nadapt = 0       # ladder updates so far
+        self.nrecorded = 0    # iterations in _moments
+        self.recording = False
         self.iteration = 0
         self.nswaps = 0  # exchange sweeps so far
         self.nevals = 0
@@ -201,6 +251,22 @@ class PTSampler:
                                         _lib.stream_handle()), "rvm_pt_swap")
         self.nswaps += 1
 
+    def _ladder_update(self, kappa, moments):
+        _lib.check(self.lib.rvm_pt_ladder_update(self.ntemps, self.halfk, self.nswapped.data_ptr(),
+                                                 self.lnp[0].data_ptr(), self.lnp[1].data_ptr(), kappa,
+                                                 self._betas.data_ptr(), self._swap_prev.data_ptr(),
+                                                 self._ratios.data_ptr(), self._n_refused.data_ptr(),
+                                                 self._moments.data_ptr() if moments else 0, self._work.data_ptr(),
+                                                 _lib.stream_handle()), "rvm_pt_ladder_update")
+
+    def adapt_ladder(self):
+        """One update of the ladder from the exchanges since the previous one (step() calls this
+        after every exchange sweep while adapt is on).  kappa comes from the host's count of
+        updates: nothing is read back from the device."""
+        kappa = (self.adaptation_lag / (self.nadapt + self.adaptation_lag)) / self.adaptation_time
+        self._ladder_update(kappa, False)
+        self.nadapt += 1
+
     def step(self, draws=None):
         """One iteration: both half-steps of every temperature, then (every swap_every iterations)
         the exchange sweep; on the stream the sampler was built on (engine.check_stream).
@@ -224,6 +290,11 @@ class PTSampler:
             self.half_step(half, u12, u3)
         if (self.iteration + 1) % self.swap_every == 0:
             self.swap(draws.get("swap"))
+            if self.adapt:
+                self.adapt_ladder()
+        if self.recording:
+            self._ladder_update(0.0, True)  # kappa = 0: the betas stay bit for bit
+            self.nrecorded += 1
         self.iteration += 1
         engine.periodic_fault_check(self, self.plan)
 
@@ -251,16 +322,65 @@ class PTSampler:
         """Accepted exchanges per sweep of each neighbouring pair (p, p + 1), [T-1]."""
         return self.nswapped.sum(1).cpu().numpy() / (max(self.nswaps, 1) * self.k)
 
+    # ---- the ladder and the evidence ---------------------------------------------------------------
+    def ladder(self):
+        """The device's betas [T] (also refreshes the host attribute `betas`)."""
+        self.betas = self._betas.cpu().numpy().copy()
+        return self.betas.copy()
+
+    def last_swap_ratios(self):
+        """Exchanges per walker of each pair between the last two ladder updates, [T-1]."""
+        return self._ratios.cpu().numpy()
+
+    def ladder_refusals(self):
+        """Updates refused because their result was no strictly decreasing finite ladder."""
+        return int(self._n_refused.item())
+
+    def freeze_ladder(self):
+        """Turn the adaptation off (the chain satisfies detailed balance from here on)."""
+        self.adapt = False
+        self.ladder()
+
+    def record_lnprob(self, on=True):
+        """While on, every step() adds that iteration's sum of lnp and of lnp^2 per temperature into
+        a device accumulator.  The moments belong to one fixed ladder: refused while adapt is on."""
+        if on and self.adapt:
+            raise ValueError("record_lnprob needs a fixed ladder: freeze_ladder() first")
+        if on and self.ntemps < 2:
+            raise ValueError("record_lnprob needs at least two temperatures")
+        self.recording = bool(on)
+
+    def mean_lnprob(self):
+        """(mean [T], std [T]) of the untempered lnp over the walkers and the recorded iterations."""
+        if self.nrecorded < 1:
+            raise ValueError("nothing recorded: record_lnprob(True), then step()")
+        m = self._moments.cpu().numpy()
+        n = float(self.nrecorded * self.k)
+        mean = m[:, 0] / n
+        return mean, np.sqrt(np.maximum(m[:, 1] / n - mean * mean, 0.0))
+
+    def log_evidence_ratio(self):
+        """(estimate, coarse): the thermodynamic integral of mean_lnprob over beta from beta_{T-1} up
+        to 1 by the trapezoid rule, and the same over every second temperature (emcee's
+        discretisation-error estimate is their difference).  This is ln Z(beta = 1) - ln Z(beta_{T-1}),
+        NOT an absolute evidence: the hard prior is improper in a and m, so ln Z(0) does not exist
+        (which is also why beta = 0 is refused)."""
+        return log_evidence_ratio(self.ladder(), self.mean_lnprob()[0])
+
     # ---- checkpoint / resume ---------------------------------------------------------------------
     def checkpoint(self, path):
         """The whole ladder to an .npz: positions [T][W][dim], lnprob [T][W], the accept and swap
-        counters, iteration, seed, stretch scale and betas.  The draws are counter-based (keyed by
-        seed, iteration and walker), so a restored sampler continues bit-identically."""
+        counters, iteration, seed, stretch scale, the current betas, and the ladder dynamics' and the
+        moments' state.  The draws are counter-based (keyed by seed, iteration and walker), so a
+        restored sampler continues bit-identically, in mid-adaptation too."""
         np.savez(path, positions=self.positions(), lnprob=self.lnprob(),
                  naccepted=self._join([self.naccepted[0], self.naccepted[1]]).cpu().numpy(),
                  nswapped=self.nswapped.cpu().numpy(), iteration=self.iteration, nswaps=self.nswaps,
-                 nevals=self.nevals, seed=np.uint64(self.seed), a=self.a, betas=self.betas,
-                 swap_every=self.swap_every)
+                 nevals=self.nevals, seed=np.uint64(self.seed), a=self.a, betas=self.ladder(),
+                 swap_every=self.swap_every, swap_totals_prev=self._swap_prev.cpu().numpy(),
+                 swap_ratios=self._ratios.cpu().numpy(), nadapt=self.nadapt, n_refused=self.ladder_refusals(),
+                 adapt=self.adapt, adaptation_lag=self.adaptation_lag, adaptation_time=self.adaptation_time,
+                 lnp_moments=self._moments.cpu().numpy(), nrecorded=self.nrecorded, recording=self.recording)
 
     def restore(self, path):
         """Load a checkpoint written by checkpoint() (same ntemps, nwalkers and dim)."""
@@ -277,3 +397,11 @@ class PTSampler:
         self.nswapped = torch.as_tensor(d["nswapped"].astype(np.int32), device=self.device).contiguous()
         self.iteration, self.nswaps, self.nevals = int(d["iteration"]), int(d["nswaps"]), int(d["nevals"])
         self.seed, self.a, self.swap_every = int(d["seed"]), float(d["a"]), int(d["swap_every"])
+        if "swap_totals_prev" not in d:  # written before the ladder could adapt: nothing more to load
+            return
+        dev = lambda k: torch.as_tensor(d[k], device=self.device).contiguous()  # noqa: E731
+        self._swap_prev, self._ratios, self._moments = dev("swap_totals_prev"), dev("swap_ratios"), dev("lnp_moments")
+        self._n_refused = torch.as_tensor([int(d["n_refused"])], dtype=torch.int64, device=self.device)
+        self.nadapt, self.nrecorded = int(d["nadapt"]), int(d["nrecorded"])
+        self.adapt, self.recording = bool(d["adapt"]), bool(d["recording"])
+        self.adaptation_lag, self.adaptation_time = float(d["adaptation_lag"]), float(d["adaptation_time"])

@@ -14,6 +14,12 @@ Each part runs in a child process of its own under its own time limit; a part th
 out of time ends the run (nothing more is started on the GPU).  Prints ONE JSON line.  The figures
 are recorded (profiles/pt_bench.json), not asserted: hot temperatures propose wider moves, which
 need more of the adaptive resolution's refinement per evaluation.
+
+--adapt runs the `pt` part alone with the ladder adapting through the burn-in (PTSampler(adapt=True),
+ptemcee's default lag and time unless given), freezes the ladder, times as above, then records the
+lnp moments for --steps more iterations (mean lnp, the thermodynamic integral), and sets the figures
+against the fixed ladder's in profiles/pt_bench.json.  It writes the line to --out
+(profiles/pt_adapt_bench.json) as well.
 """
 import argparse
 import json
@@ -48,6 +54,11 @@ def parse():
                     help="seconds each part's process may take (the ladder's 4000-iteration burn-in alone takes "
                          "about ten minutes: the hot temperatures' first few hundred iterations out of the tight "
                          "ball run at 0.1-0.3 s each)")
+    ap.add_argument("--adapt", action="store_true", help="adapt the ladder during the burn-in, then freeze it")
+    ap.add_argument("--adaptation-lag", type=float, default=10000.0)
+    ap.add_argument("--adaptation-time", type=float, default=100.0)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pt_adapt_bench.json"),
+                    help="where --adapt writes its line")
     ap.add_argument("--part", choices=("pt", "ensemble"), default=None, help="(internal) run one part in this process")
     return ap.parse_args()
 
@@ -68,7 +79,9 @@ def run_part(args):
     if args.part == "pt":
         T, W = args.ntemps, args.walkers
         X0 = state.get_params()[None, None] + 0.1e-2 * scales * np.random.normal(size=(T, W, state.Nvars))
-        smp = PTSampler(T, W, state, obs, seed=2017, swap_every=args.swap_every)
+        smp = PTSampler(T, W, state, obs, seed=2017, swap_every=args.swap_every, adapt=args.adapt,
+                        adaptation_lag=args.adaptation_lag, adaptation_time=args.adaptation_time)
+        betas_start = [float(b) for b in smp.betas]
         nwalk = T * W
     else:
         T, W = 1, args.ensemble_walkers
@@ -87,6 +100,8 @@ def run_part(args):
         if i % 64 == 0 and time.perf_counter() - t_prog > 20.0:
             t_prog = time.perf_counter()
             print(f"pt_bench[{args.part}]: burn-in iteration {i}", file=sys.stderr, flush=True)
+    if args.part == "pt" and args.adapt:
+        smp.freeze_ladder()  # the warmup and the timed iterations run on the adapted, fixed ladder
     for _ in range(args.warmup):
         smp.step()
     burn = smp.plan.faults(reset=True)
@@ -115,6 +130,20 @@ def run_part(args):
                    acceptance=[float(a) for a in acc],
                    swap_fraction=[float(v) for v in (smp.nswapped - sw0).sum(1).cpu().numpy() / float(sweeps * W)],
                    mean_lnprob=[float(v) for v in lnp.mean(1)], all_lnprob_finite=bool(np.isfinite(lnp).all()))
+        if args.adapt:
+            out.update(adapt=True, adaptation_lag=args.adaptation_lag, adaptation_time=args.adaptation_time,
+                       betas_start=betas_start, ladder_updates=smp.nadapt, ladder_refusals=smp.ladder_refusals())
+            smp.record_lnprob(True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                smp.step()
+            torch.cuda.synchronize()
+            out["ms_per_iteration_recording"] = 1e3 * (time.perf_counter() - t0) / args.steps
+            mean, std = smp.mean_lnprob()
+            est, coarse = smp.log_evidence_ratio()
+            out.update(recorded_mean_lnprob=[float(v) for v in mean], recorded_std_lnprob=[float(v) for v in std],
+                       log_evidence_ratio=est, log_evidence_ratio_coarse=coarse)
     else:
         out.update(walkers=W, fused=False,
                    acceptance=float((smp.naccepted - acc0).sum().item()) / float(W * args.steps))
@@ -128,7 +157,7 @@ def main():
         return
     result = {"metric": "walker-logL evals/sec, parallel-tempering ensemble (2-planet, 100 obs, steady state)",
               "unit": "evals/s"}
-    for part in ("pt", "ensemble"):
+    for part in (("pt",) if args.adapt else ("pt", "ensemble")):
         cmd = [sys.executable, os.path.abspath(__file__), "--part", part] + sys.argv[1:]
         try:
             p = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=args.part_timeout, check=False)
@@ -138,7 +167,16 @@ def main():
             sys.exit(f"pt_bench: part '{part}' ended with status {p.returncode}; stopping")
         result[part] = json.loads(p.stdout.decode().strip().splitlines()[-1])
     result["value"] = result["pt"]["evals_per_s"]
-    result["pt_over_ensemble"] = result["pt"]["evals_per_s"] / result["ensemble"]["evals_per_s"]
+    if args.adapt:
+        with open(os.path.join(ROOT, "profiles", "pt_bench.json")) as f:
+            fixed = json.load(f)["pt"]
+        result["fixed_ladder"] = {k: fixed[k] for k in ("betas", "swap_fraction", "ms_per_iteration", "evals_per_s")}
+        result["min_swap_fraction"] = min(result["pt"]["swap_fraction"])
+        result["fixed_ladder_min_swap_fraction"] = min(fixed["swap_fraction"])
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result) + "\n")
+    else:
+        result["pt_over_ensemble"] = result["pt"]["evals_per_s"] / result["ensemble"]["evals_per_s"]
     print(json.dumps(result))
 
 
