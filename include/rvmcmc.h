@@ -177,6 +177,13 @@ int rvm_plan_counters(rvm_plan* plan, int32_t reset, int64_t* out, int32_t n, vo
  * a plan without a hedge (RVM_HEDGE=0).  Synchronises the stream. */
 int rvm_plan_hedge_stats(rvm_plan* plan, int32_t reset, int64_t* hedged, int64_t* replayed, int64_t* missed,
                          void* stream);
+/* The hedge's early stop (the refinement kernel marks, at its start, the hedge blocks whose
+ * group has no walker slot on its work lists, and they stop; RVM_HEDGE_MARK=0 at plan creation: never), since
+ * the last reset: marked = (group, direction) marks written, gave_up = hedge blocks that stopped on their mark
+ * (a block that had completed before its mark came is not counted, so gave_up <= marked).  Reset semantics
+ * and the dependence on timing as rvm_plan_hedge_stats; all zero on a plan without a hedge.  Either pointer
+ * may be NULL.  Synchronises the stream. */
+int rvm_plan_hedge_marks(rvm_plan* plan, int32_t reset, int64_t* marked, int64_t* gave_up, void* stream);
 /* Kernel timing (benchmarks): the plan's next max_launches likelihood evaluations (any entry point)
  * record HIP events on their stream around the likelihood kernel and around the refinement kernel
  * that follows it (0..4096; 0 stops).  rvm_plan_kernel_times waits for those events and returns

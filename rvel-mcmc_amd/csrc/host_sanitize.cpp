@@ -52,6 +52,8 @@ int main() {
     expect(rvm_plan_create(&cfg, tn.data(), rv.data(), sg.data(), (int)t.size(), 64, &plan) < 0, "nan epoch");
     expect(std::strlen(rvm_last_error()) > 0, "last_error");
     expect(rvm_logl_batch(nullptr, 1, nullptr, 1.0, nullptr, nullptr, nullptr, nullptr) < 0, "logl null plan");
+    int64_t mk = -1, gu = -1;
+    expect(rvm_plan_hedge_marks(nullptr, 0, &mk, &gu, nullptr) < 0 && mk == -1 && gu == -1, "hedge_marks null plan");
     rvm_param_map pm{};
     expect(rvm_stretch_half_step(nullptr, &pm, 10, 1, 0, nullptr, nullptr, nullptr, 1, nullptr, 2.0, 0, 0, 0, 1.0,
                                  nullptr, nullptr, nullptr, nullptr) < 0,

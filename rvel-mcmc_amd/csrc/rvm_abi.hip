@@ -605,6 +605,7 @@ int rvm_plan_create(const rvm_config* cfg, const double* t, const double* rv, co
     // the events: RVM_HEDGE=0 turns it off, RVM_HEDGE_GROUPS caps its groups (1 .. RVM_HEDGE_GROUPS_MAX;
     // INTEGRATION.md).
     P.hedge_groups = 0;
+    P.hedge_mark = 0;
     P.hrv = nullptr;
     P.hsum = nullptr;
     P.hslot = nullptr;
@@ -632,6 +633,8 @@ int rvm_plan_create(const rvm_config* cfg, const double* t, const double* rv, co
                 P.htab = P.hslot + n_slot;
                 P.hw = P.htab + max_walkers;
                 P.hedge_groups = hgroups;
+                const char* hm = getenv("RVM_HEDGE_MARK");  // (A/B knob: 0 leaves unneeded hedge blocks to the cancel)
+                P.hedge_mark = hm && hm[0] == '0' ? 0 : 1;
             } else {
                 (void)hipGetLastError();
                 if (plan->hmem) (void)hipFree(plan->hmem);
@@ -781,6 +784,22 @@ int rvm_plan_hedge_stats(rvm_plan* plan, int32_t reset, int64_t* hedged, int64_t
     if (hedged) *hedged = (int64_t)h[0];
     if (replayed) *replayed = (int64_t)h[1];
     if (missed) *missed = (int64_t)h[2];
+    return 0;
+}
+
+int rvm_plan_hedge_marks(rvm_plan* plan, int32_t reset, int64_t* marked, int64_t* gave_up, void* stream) {
+    if (!plan) return fail(-1, "rvm_plan_hedge_marks: null plan");
+    unsigned long long h[2] = {};
+    if (plan->dev.hw != nullptr) {
+        hipStream_t st = (hipStream_t)stream;
+        unsigned long long* d = plan->dev.hw + rvm::RVM_HW_STATS + 3;
+        hipError_t e = hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && reset) e = hipMemsetAsync(d, 0, sizeof(h), st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return hip_fail(e, "rvm_plan_hedge_marks");
+    }
+    if (marked) *marked = (int64_t)h[0];
+    if (gave_up) *gave_up = (int64_t)h[1];
     return 0;
 }
 

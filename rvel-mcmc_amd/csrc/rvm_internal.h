@@ -75,9 +75,13 @@ constexpr int RVM_HEDGE_CAND = RVM_HEDGE_STRIDE + 64;
 constexpr int RVM_HEDGE_MAX_W = 12288;
 // DevPlan::hw words: [0] cancel (generation << 8 | 1), [1] refinement blocks that have left,
 // [2 + 2 g + d] group g direction d complete (generation << 8 | 2), then the statistics: slots hedged,
-// pass-2 walker-directions replayed, pass-2 walker-directions integrated although the launch hedged
+// pass-2 walker-directions replayed, pass-2 walker-directions integrated although the launch hedged, [+ 3]
+// mark words written, [+ 4] hedge blocks that stopped on their mark (rvm_plan_hedge_marks);
+// then [RVM_HW_MARK + 2 g + d] group g direction d is not needed (generation << 8 | 1): none of its slots
+// is on the refinement kernel's lists in that direction
 constexpr int RVM_HW_STATS = 2 + 2 * RVM_HEDGE_GROUPS_MAX;
-constexpr int RVM_HW_WORDS = RVM_HW_STATS + 3 + 3;
+constexpr int RVM_HW_MARK = RVM_HW_STATS + 3 + 3;
+constexpr int RVM_HW_WORDS = RVM_HW_MARK + 2 * RVM_HEDGE_GROUPS_MAX;
 
 // Epoch schedule of one integration direction (t >= 0 ascending from 0, or t < 0 descending).
 struct DirSched {
@@ -201,6 +205,9 @@ struct DevPlan {
     // (generation << 16 | slot),
     // htab [rq_cap] per walker slot its hedge index (generation << 16 | index), hw [RVM_HW_WORDS]
     int32_t hedge_groups;
+    // 1: the refinement kernel marks, at its start, the hedge blocks whose group has no listed slot in their
+    // direction, and they stop (RVM_HEDGE_MARK=0 at plan creation: they run until the cancel, A/B)
+    int32_t hedge_mark;
     double* hrv;
     double* hsum;
     unsigned long long* hslot;

@@ -116,6 +116,41 @@ __device__ __forceinline__ bool claim_item(gu64* w, unsigned long long gen, unsi
     }
 }
 
+// (hedge) One wave of the refinement kernel marks the hedge blocks nobody can use (refine_kernel<.., RVM_REFINE_HM>, the grid's
+// last block when it has no task): every listed walker slot's hedge index (htab, this generation's) gives a
+// (group, direction) that some open walker may still replay; the others get their mark word
+// hw[RVM_HW_MARK + 2 g + d] = generation << 8 | 1, and their count goes to hw[RVM_HW_STATS + 3]
+// (rvm_plan_hedge_marks).  n0, n1, n2: the sizes of the lists (both directions open, forward only, backward
+// only); hedge: the launch's hedge blocks; wpb: walker slots per hedge group.  No LDS, no barrier: each lane
+// gathers the needed blocks of its share of the lists in a bit mask, the wave ORs them.
+__device__ __forceinline__ void hedge_mark_unneeded(const int32_t* rq_w, const int rq_cap,
+                                                    const unsigned long long* htab, unsigned long long* hw_,
+                                                    const int n0, const int n1, const int n2,
+                                                    const unsigned long long gen, const int hedge, const int wpb) {
+    const int lane = threadIdx.x & 63;
+    unsigned need = 0;
+    for (int l2 = 0; l2 < 3; l2++) {
+        int n = l2 == 0 ? n0 : (l2 == 1 ? n1 : n2);
+        n = n < rq_cap ? n : rq_cap;
+        for (int i = lane; i < n; i += 64) {
+            const int wl = rq_w[(size_t)l2 * rq_cap + i];
+            if (wl < 0 || wl >= rq_cap) continue;
+            const unsigned long long tb = __hip_atomic_load((gu64*)htab + wl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int hg = (int)(tb & 0xFFFF) / wpb;
+            if ((tb >> 16) != gen || hg >= RVM_HEDGE_GROUPS_MAX) continue;
+            if (l2 != 2) need |= 1u << (2 * hg);
+            if (l2 != 1) need |= 1u << (2 * hg + 1);
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) need |= (unsigned)__shfl_xor((int)need, d, 64);
+    gu64* hw = (gu64*)hw_;
+    const bool mark = lane < hedge && lane < 2 * RVM_HEDGE_GROUPS_MAX && !((need >> lane) & 1u);
+    if (mark) __hip_atomic_store(hw + RVM_HW_MARK + lane, (gen << 8) | 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long nm = __builtin_popcountll(ballot(mark));
+    if (lane == 0 && nm)
+        __hip_atomic_fetch_add(hw + RVM_HW_STATS + 3, nm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Bounded wait of a refinement pass's hand-off (split exchange, team B for team A): the partner
 // integrates a pass of 2^rf x the base steps without publishing progress, so the allowance scales
 // with the pass (a deep pass is no timeout; the timeout stays a last-resort fault)
@@ -140,11 +175,17 @@ struct DirState {
 // give every workgroup one direction anyway, where waves 4..7 of an 8-wave group only waited at the
 // barriers -- and a wave may then hold up to 512 registers (AGPRs too) instead of 256: no scratch
 // spill (round 5: 400 B per lane, 13.6 MB per steady-state launch; tests/test_kernel_resources.py).
+// NW = RVM_REFINE_HM (5): four waves, and the instantiation that marks the hedge blocks nobody can use (HM
+// below), launched for hedged launches of plans with DevPlan::hedge_mark.  The marking is compiled into that
+// instantiation alone: in the others it changed the register allocation of every launch's pass loops --
+// launches without a hedge too (3 planets, 8192 walkers: +0.5 % per iteration).
+constexpr int RVM_REFINE_HM = 5;
 template <int NP, bool D3, int NW>
-__global__ __launch_bounds__(NW * 64) void refine_kernel(const DevPlan P, const int W, const double* __restrict__ params,
-                                                     const double hill_factor, double* __restrict__ rv_out,
-                                                     double* __restrict__ logl_out, int32_t* __restrict__ status_out,
-                                                     const StretchArgs sa, const int eager, const int hedge) {
+__global__ __launch_bounds__((NW == RVM_REFINE_HM ? 4 : NW) * 64) void refine_kernel(
+    const DevPlan P, const int W, const double* __restrict__ params, const double hill_factor,
+    double* __restrict__ rv_out, double* __restrict__ logl_out, int32_t* __restrict__ status_out, const StretchArgs sa,
+    const int eager, const int hedge) {
+    constexpr bool HM = NW == RVM_REFINE_HM;
     constexpr int L = LanesPerWalker<NP>::value;
     constexpr int WPB = 64 / L;
     constexpr int PR = D3 ? 7 : 5;
@@ -254,6 +295,16 @@ __global__ __launch_bounds__(NW * 64) void refine_kernel(const DevPlan P, const 
                         ((int)gridDim.x & 1) == 0 && 2 * ngw <= (int)gridDim.x;
     const int ntask = eager ? (esplit ? 2 * ngw : ngw) : (team ? ntask_team : (split ? ntask_split : ng));
     if ((int)blockIdx.x >= ntask) {
+        // (hedge) the grid's last block, when it has no task: the hedge blocks whose group has none of its
+        // slots on the lists in their direction are not needed -- no open walker can come to replay them --
+        // and are told so (hw[RVM_HW_MARK ..], the eager protocol's eflag[0] rule), so that only blocks
+        // some walker may still use are integrating when this kernel ends and the join waits for them.
+        // A listed slot whose hedge index is not in yet (a block dispatched late) counts for nothing: its
+        // group may stop, and the slot's pass 2 is integrated here as for any slot not hedged.
+        if constexpr (HM) {
+            if (hedge && blockIdx.x == gridDim.x - 1 && wv == 0)
+                hedge_mark_unneeded(P.rq_w, P.rq_cap, P.htab, P.hw, nq[0], nq[1], nq[2], gen, hedge, WPB);
+        }
         leave();
         return;
     }
@@ -1367,9 +1418,12 @@ static hipError_t launch_eager_t(const DevPlan& P, int W, const double* params, 
 // the pass's RV per epoch, chi2, estimate and encounter flag write-through, then its completion word --
 // eager_kernel's layout and combiner.  The refinement kernel, when a group comes to pass 2, replays it
 // from these if they are complete for every open walker-direction of the group, and integrates it as
-// before if not: it never waits.  Its last block out sets the cancel word, which the hedge blocks
-// test before they start, every 64 steps and at every epoch; run_logl then joins the side stream and
-// advances the launch generation (gen_bump_kernel), as after an eager launch.
+// before if not: it never waits.  At its start it marks the (group, direction) blocks none of whose slots
+// is on its lists (hw[RVM_HW_MARK ..]; DevPlan::hedge_mark), and its last block out sets the cancel word;
+// the hedge blocks test the cancel before they start, every 64 steps and at every epoch, and their mark before
+// they start and at every epoch, so that few of them
+// are still integrating when run_logl joins the side stream and advances the launch generation
+// (gen_bump_kernel), as after an eager launch.
 template <int NP, bool D3>
 __global__ __launch_bounds__(256) void hedge_kernel(const DevPlan P, const int W, const double hill_factor,
                                                     const StretchArgs sa, const int ngrp, const int skip) {
@@ -1404,9 +1458,29 @@ __global__ __launch_bounds__(256) void hedge_kernel(const DevPlan P, const int W
     __syncthreads();
     const unsigned long long gen = s_gen;
     const unsigned long long ctag = (gen << 8) | 1ull;
-    if (tid == 0) s_cancel[0] = __hip_atomic_load(hw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ctag;
+    // (the block's own mark word: the refinement kernel marks a group and direction none of whose slots it
+    // lists.  Read at the epochs only, its address formed where it is read -- the marks come ~0.6 ms before the
+    // launch's end, and the step loop keeps the cancel word alone, as before; s_marked: the block stops on it)
+    __shared__ int s_marked;
+    auto stopped = [&]() {
+        const bool mk = __hip_atomic_load(hw + RVM_HW_MARK + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ctag;
+        if (mk) s_marked = 1;
+        return mk || __hip_atomic_load(hw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ctag;
+    };
+    if (tid == 0) {
+        s_marked = 0;
+        s_cancel[0] = stopped();
+    }
     __syncthreads();
-    if (s_cancel[0]) return;  // (before the slots are read)
+    // (a block that stops on its mark is counted: hw[RVM_HW_STATS + 4], rvm_plan_hedge_marks)
+    auto count_marked = [&]() {
+        if (tid == 0 && s_marked)
+            __hip_atomic_fetch_add(hw + RVM_HW_STATS + 4, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    if (s_cancel[0]) {  // (before the slots are read)
+        count_marked();
+        return;
+    }
     const unsigned long long kbad = ~0ull;
     for (int i = tid; i < RVM_HEDGE_CAND; i += 256) {
         s_ck[i] = kbad;
@@ -1599,8 +1673,7 @@ __global__ __launch_bounds__(256) void hedge_kernel(const DevPlan P, const int W
             const double v0 = star_vx<NP, L>(s);
             if (pl_idx == 0) s_rv[e & 1][k_u][slot] = v0;
         }
-        if (wv == 0 && lane == 0)
-            s_cancel[e & 1] = __hip_atomic_load(hw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ctag;
+        if (wv == 0 && lane == 0) s_cancel[e & 1] = stopped();
         __syncthreads();
         if (s_cancel[e & 1]) {
             cancelled = true;
@@ -1631,13 +1704,18 @@ __global__ __launch_bounds__(256) void hedge_kernel(const DevPlan P, const int W
         o[11] = (unsigned long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_REG_HW_ID
     }
 #endif
-    if (cancelled) return;
+    if (cancelled) {
+        count_marked();
+        return;
+    }
     if (work && pl_idx == 0) s_enc[k_u][slot] = (int)(((s.encm >> lane) & kick_enc_bits<NP>()) != 0);
     __syncthreads();
     if (wv == 0) {
         // (a cancel that stopped another wave inside the last segment: seen here, after the barrier)
-        if (__builtin_amdgcn_readfirstlane((int)(__hip_atomic_load(hw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ctag)))
+        if (__builtin_amdgcn_readfirstlane((int)stopped())) {
+            count_marked();
             return;
+        }
         if (cmb) {
             int er = 0;
             for (int q = 0; q < nl; q++) er |= s_enc[q][lane];
@@ -1755,7 +1833,11 @@ static hipError_t launch_refine_t(const DevPlan& P, int W, const double* params,
     const int groups = (W + wpb - 1) / wpb + 2;
     int nb = std::max(2, std::min(P.n_cu > 0 ? P.n_cu : 256, 2 * groups));
     nb &= ~1;
-    if (w4)
+    // (a hedged launch of a plan that marks the unneeded hedge blocks: the kernel with the marking compiled in)
+    if (w4 && hedge && P.hedge_mark && smem <= refine_budget<NPV, D3V, RVM_REFINE_HM>())
+        refine_kernel<NPV, D3V, RVM_REFINE_HM><<<dim3(nb), dim3(256), smem, stream>>>(P, W, params, hill_factor, rv_out,
+                                                                                      logl, status, sa, eager, hedge);
+    else if (w4)
         refine_kernel<NPV, D3V, 4><<<dim3(nb), dim3(256), smem, stream>>>(P, W, params, hill_factor, rv_out, logl, status,
                                                                           sa, eager, hedge);
     else
@@ -1771,6 +1853,7 @@ static hipError_t prepare_refine_t(const DevPlan& P) {
     const size_t smem = (size_t)emax * 8 * sizeof(double);
     const size_t b = std::min(refine_budget<NPV, D3V, 4>(), refine_budget<NPV, D3V, 8>());
     if (P.hedge_groups > 0) (void)hedge_budget<NPV, D3V>();  // (the hedge kernel's LDS attribute, set here once)
+    if (P.hedge_groups > 0 && P.hedge_mark) (void)refine_budget<NPV, D3V, RVM_REFINE_HM>();  // (the marking instantiation's)
     return smem <= b ? hipSuccess : hipErrorInvalidConfiguration;
 }
 

@@ -232,6 +232,15 @@ class LoglPlan:
                                                  _lib.stream_handle(stream)), "rvm_plan_hedge_stats")
         return dict(hedged=h.value, replayed=r.value, missed=m.value)
 
+    def hedge_marks(self, reset=False, stream=None) -> dict:
+        """rvm_plan_hedge_marks (synchronises the stream): hedge (group, direction) marks the refinement kernel
+        wrote because no listed walker slot could use the block, and hedge blocks that stopped on theirs.
+        Timing-dependent, as hedge_stats()."""
+        m, g = C.c_int64(), C.c_int64()
+        _lib.check(self.lib.rvm_plan_hedge_marks(self._h, int(bool(reset)), C.byref(m), C.byref(g),
+                                                 _lib.stream_handle(stream)), "rvm_plan_hedge_marks")
+        return dict(marked=m.value, gave_up=g.value)
+
     def check_faults(self, what="plan", stream=None, group=None) -> dict:
         """Raise RvmError on hand-off timeouts, NONFINITE results, or (a plan that refines, resolve_max
         > 0) UNRESOLVED results since the last check: emcee raises on a NaN log-probability
