@@ -475,6 +475,49 @@ int rvm_logl_derivs(const rvm_plan* plan, int32_t n_chains, const double* params
                     const int32_t* dir_rows, double hill_factor, double* logl_out, double* grad_out, double* hess_out,
                     int32_t* status_out, void* workspace, void* stream);
 
+/* ---- the recorded chain and its autocovariance ---------------------------------------------------
+ * Replaces the host side of the reference's production workflow (driver.py:86-120 run loop filling a
+ * host chain every iteration; driver.py:265-414 trim, autocorrelation times, efficacy): the chain stays
+ * in device memory and only the [n_params][n_lags] autocovariance crosses to the host.
+ * A chain buffer is [n_steps][n_params][n_cols] float64 -- one step slot is the SoA block
+ * [n_params][n_cols] every sampler holds -- with an optional log-probability buffer [n_steps][n_cols].
+ * The conventions above hold for the three launch functions: device pointers, no allocation, no
+ * synchronisation, stream-ordered and capturable, no floating-point atomics (the same bits from run to
+ * run); argument errors return < 0 before any HIP call and name the argument in rvm_last_error.
+ * n_params is 1 .. 65534 and n_cols 1 .. 16776960 (a grid's y and z extents).
+ *
+ * record: one segment of a sampler's positions src [n_params][src_ld] into one step slot dst
+ *   [n_params][dst_ld] (dst points AT the slot): dst[p][dst_col0 + j] = src[p][src_col0 + j col_stride],
+ *   j < n_cols; with the nullable pair lnp_src [src_ld] / lnp_dst [dst_ld] (both or neither) also
+ *   lnp_dst[dst_col0 + j] = lnp_src[src_col0 + j col_stride].  One launch per segment (the two halves of
+ *   the stretch ensemble, the cold temperature's columns of each tempering half, the chains of MH / SMALA).
+ * moments, per column (p, w) over the steps [t0, t1), n = t1 - t0, every sum left to right:
+ *   mean_out[p][w] = (x[t0] + x[t0+1] + ... + x[t1-1]) / n ;  m2_out[p][w] = sum_t (x[t] - mean)^2
+ *   (x - mean rounded, its square rounded, then added: no fused multiply-add).
+ * autocov, for the lags k = lag0 .. lag0 + n_lags - 1 (each <= n - 1; n_lags <= 2^30 and
+ *   n_params * n_lags within int32):
+ *   acov_out[p][k - lag0] = (1/W) sum_w sum_{t = t0}^{t1 - 1 - k} y[t] y[t + k],   W = n_cols,
+ *   y = x - mean[p][w] rounded at use, mean [n_params][n_cols] as rvm_chain_moments wrote it.  This is
+ *   the unnormalised sum that irfft(f conj f) of the zero-padded y gives (driver.integrated_time).
+ *   The order of the sum is fixed:
+ *     1. per walker, t ascending in one thread, acc = fma(y[t], y[t + k], acc) from acc = 0;
+ *     2. the walkers of a block of 256 (walker block b: w in [256 b, 256 b + 256), absent walkers add
+ *        +0) by a binary tree over the 256 slots, slot i += slot i + h for h = 128, 64, ..., 1;
+ *     3. the walker blocks in index order, b = 0, 1, ..., in a second small launch, then one division
+ *        by W.
+ *   workspace: rvm_chain_autocov_workspace_bytes(n_params, n_cols, n_lags) bytes (8 n_params x n_lags
+ *   rounded up to a multiple of 16 x ceil(n_cols / 256); 0 on bad arguments) that carry the blocks'
+ *   partial sums from the first launch to the second (contents unspecified before and after).
+ *   Only the lags asked for are computed: a caller that has lags [0, 64) asks for [64, 128) next. */
+int rvm_chain_record(int32_t n_params, int32_t n_cols, const double* src, int64_t src_ld, int64_t src_col0,
+                     int64_t col_stride, double* dst, int64_t dst_ld, int64_t dst_col0, const double* lnp_src,
+                     double* lnp_dst, void* stream);
+int rvm_chain_moments(const double* chain, int32_t n_params, int32_t n_cols, int64_t t0, int64_t t1, double* mean_out,
+                      double* m2_out, void* stream);
+size_t rvm_chain_autocov_workspace_bytes(int32_t n_params, int32_t n_cols, int32_t n_lags);
+int rvm_chain_autocov(const double* chain, const double* mean, int32_t n_params, int32_t n_cols, int64_t t0, int64_t t1,
+                      int32_t lag0, int32_t n_lags, double* acov_out, void* workspace, void* stream);
+
 const char* rvm_last_error(void);
 int rvm_abi_version(void);
 

@@ -86,6 +86,21 @@ int main() {
     expect(rvm_pt_ladder_update(1, 4, nullptr, nullptr, nullptr, 0.5, nullptr, nullptr, nullptr, nullptr, nullptr,
                                 nullptr, nullptr) == 0,
            "pt ladder of one temperature");
+    // the recorded chain: refusals before any HIP call, the column and lag bounds in 64-bit arithmetic
+    expect(rvm_chain_record(2, 4, &d1, 16, 0, INT64_MAX, &d1, 8, 0, nullptr, nullptr, nullptr) < 0,
+           "chain record stride overflow");
+    expect(rvm_chain_record(2, 4, &d1, 16, 0, 1, &d1, INT64_MAX, INT64_MAX - 1, nullptr, nullptr, nullptr) < 0,
+           "chain record dst_col0 overflow");
+    expect(rvm_chain_record(2, 4, &d1, 16, 0, 1, &d1, 8, 0, &d1, nullptr, nullptr) < 0, "chain record lone lnp_src");
+    expect(rvm_chain_moments(&d1, 2, 4, 5, 5, &d1, &d1, nullptr) < 0, "chain moments empty range");
+    expect(rvm_chain_autocov(&d1, &d1, 2, 4, 0, 10, INT32_MAX, 1 << 30, &d1, &d1, nullptr) < 0,
+           "chain autocov lag overflow");
+    expect(rvm_chain_autocov(&d1, &d1, 65534, 4, 0, INT64_MAX, 0, 1 << 30, &d1, &d1, nullptr) < 0,
+           "chain autocov n_params * n_lags");
+    expect(rvm_chain_autocov_workspace_bytes(10, 200, 17) == (size_t)8 * 10 * 32, "chain autocov workspace");
+    expect(rvm_chain_autocov_workspace_bytes(1, 65535 * 256, 1 << 30) == (size_t)8 * ((size_t)1 << 30) * 65535,
+           "chain autocov workspace, largest");
+    expect(rvm_chain_autocov_workspace_bytes(65534, 4, 1 << 30) == 0, "chain autocov workspace, refused");
     expect(rvm_mh_accept(0, 1, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr) < 0, "mh bad");
     expect(rvm_fd_params(10, 1, nullptr, 1e-6, nullptr, nullptr, nullptr) < 0, "fd bad");
     const int32_t rows[2] = {0, 0};

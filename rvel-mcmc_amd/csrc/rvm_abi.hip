@@ -61,6 +61,13 @@ hipError_t launch_pt_swap(int P, int T, int Wh, const double* betas, double* x0,
                           double* lnp1, uint64_t seed, uint64_t it, const double* draws, int32_t* swapped,
                           hipStream_t st);
 hipError_t launch_pt_ladder_update(const PtLadderArgs& g, hipStream_t st);
+hipError_t launch_chain_record(int P, int n, const double* src, int64_t src_ld, int64_t c0, int64_t cs, double* dst,
+                               int64_t dst_ld, int64_t d0, const double* lsrc, double* ldst, hipStream_t st);
+hipError_t launch_chain_moments(const double* x, int P, int W, int64_t t0, int64_t t1, double* mean, double* m2,
+                                hipStream_t st);
+size_t chain_autocov_workspace_doubles(int P, int W, int n_lags);
+hipError_t launch_chain_autocov(const double* x, const double* mean, int P, int W, int64_t t0, int64_t t1, int lag0,
+                                int n_lags, double* acov, double* part, hipStream_t st);
 hipError_t launch_fd_params(int P, int n, const double* x, double rel, const double* fl, double* out, hipStream_t st);
 hipError_t launch_smala_derive(int P, int C, int E, const double* x, double rel, const double* fl,
                                const double* lp_st, const int32_t* st_st, const double* rv, const double* w,
@@ -1107,6 +1114,71 @@ int rvm_pt_ladder_update(int32_t n_temps, int32_t n_half, const int32_t* swapped
     g.ws_moments = (double*)workspace + (n_temps - 1);
     hipError_t e = rvm::launch_pt_ladder_update(g, (hipStream_t)stream);
     return e == hipSuccess ? 0 : hip_fail(e, "rvm_pt_ladder_update");
+}
+
+// ---- the recorded chain (rvm_chain.hip) ----
+// (a kernel grid's y and z extents hold 65535 blocks: the parameter rows, the blocks of 256 walkers)
+static const char* chain_bad_shape(int32_t n_params, int32_t n_cols) {
+    if (n_params < 1 || n_params > 65534) return "n_params must be 1 .. 65534";
+    if (n_cols < 1 || n_cols > 65535 * 256) return "n_cols must be 1 .. 16776960";
+    return nullptr;
+}
+
+int rvm_chain_record(int32_t n_params, int32_t n_cols, const double* src, int64_t src_ld, int64_t src_col0,
+                     int64_t col_stride, double* dst, int64_t dst_ld, int64_t dst_col0, const double* lnp_src,
+                     double* lnp_dst, void* stream) {
+    if (const char* m = chain_bad_shape(n_params, n_cols)) return fail(-1, std::string("rvm_chain_record: ") + m);
+    if (!src) return fail(-1, "rvm_chain_record: null src");
+    if (!dst) return fail(-1, "rvm_chain_record: null dst");
+    if (col_stride < 1) return fail(-1, "rvm_chain_record: col_stride must be >= 1");
+    if (src_col0 < 0) return fail(-1, "rvm_chain_record: src_col0 must be >= 0");
+    if (dst_col0 < 0) return fail(-1, "rvm_chain_record: dst_col0 must be >= 0");
+    if (col_stride > (INT64_MAX - src_col0) / n_cols || src_ld < src_col0 + (int64_t)(n_cols - 1) * col_stride + 1)
+        return fail(-1, "rvm_chain_record: src_ld is smaller than the last gathered column + 1");
+    if (dst_col0 > INT64_MAX - n_cols || dst_ld < dst_col0 + n_cols)
+        return fail(-1, "rvm_chain_record: dst_ld is smaller than dst_col0 + n_cols");
+    if ((lnp_src == nullptr) != (lnp_dst == nullptr))
+        return fail(-1, "rvm_chain_record: lnp_src and lnp_dst go together (both or neither)");
+    hipError_t e = rvm::launch_chain_record(n_params, n_cols, src, src_ld, src_col0, col_stride, dst, dst_ld, dst_col0,
+                                            lnp_src, lnp_dst, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rvm_chain_record");
+}
+
+int rvm_chain_moments(const double* chain, int32_t n_params, int32_t n_cols, int64_t t0, int64_t t1, double* mean_out,
+                      double* m2_out, void* stream) {
+    if (const char* m = chain_bad_shape(n_params, n_cols)) return fail(-1, std::string("rvm_chain_moments: ") + m);
+    if (!chain) return fail(-1, "rvm_chain_moments: null chain");
+    if (t0 < 0) return fail(-1, "rvm_chain_moments: t0 must be >= 0");
+    if (t1 <= t0) return fail(-1, "rvm_chain_moments: t1 must be > t0");
+    if (!mean_out) return fail(-1, "rvm_chain_moments: null mean_out");
+    if (!m2_out) return fail(-1, "rvm_chain_moments: null m2_out");
+    hipError_t e = rvm::launch_chain_moments(chain, n_params, n_cols, t0, t1, mean_out, m2_out, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rvm_chain_moments");
+}
+
+size_t rvm_chain_autocov_workspace_bytes(int32_t n_params, int32_t n_cols, int32_t n_lags) {
+    if (chain_bad_shape(n_params, n_cols) || n_lags < 1 || n_lags > (1 << 30) || (int64_t)n_params * n_lags > INT32_MAX)
+        return 0;
+    return sizeof(double) * rvm::chain_autocov_workspace_doubles(n_params, n_cols, n_lags);
+}
+
+int rvm_chain_autocov(const double* chain, const double* mean, int32_t n_params, int32_t n_cols, int64_t t0, int64_t t1,
+                      int32_t lag0, int32_t n_lags, double* acov_out, void* workspace, void* stream) {
+    if (const char* m = chain_bad_shape(n_params, n_cols)) return fail(-1, std::string("rvm_chain_autocov: ") + m);
+    if (!chain) return fail(-1, "rvm_chain_autocov: null chain");
+    if (!mean) return fail(-1, "rvm_chain_autocov: null mean");
+    if (t0 < 0) return fail(-1, "rvm_chain_autocov: t0 must be >= 0");
+    if (t1 <= t0) return fail(-1, "rvm_chain_autocov: t1 must be > t0");
+    if (lag0 < 0) return fail(-1, "rvm_chain_autocov: lag0 must be >= 0");
+    if (n_lags < 1 || n_lags > (1 << 30)) return fail(-1, "rvm_chain_autocov: n_lags must be 1 .. 2^30");
+    if ((int64_t)lag0 + n_lags > t1 - t0)
+        return fail(-1, "rvm_chain_autocov: lag0 + n_lags - 1 must be at most t1 - t0 - 1");
+    if ((int64_t)n_params * n_lags > INT32_MAX) return fail(-1, "rvm_chain_autocov: n_params * n_lags beyond int32");
+    if (!acov_out) return fail(-1, "rvm_chain_autocov: null acov_out");
+    if (!workspace) return fail(-1, "rvm_chain_autocov: null workspace");
+    hipError_t e = rvm::launch_chain_autocov(chain, mean, n_params, n_cols, t0, t1, lag0, n_lags, acov_out,
+                                             (double*)workspace, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rvm_chain_autocov");
 }
 
 int rvm_mh_propose(int32_t n_params, int32_t n_chains, int64_t chain_begin, const double* x, const double* scales,

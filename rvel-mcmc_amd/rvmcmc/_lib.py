@@ -130,6 +130,12 @@ SIGNATURES = {
                                 _dp]),
     "rvm_mh_step": (C.c_int, [C.c_void_p, C.POINTER(ParamMapC), C.c_int32, C.c_int32, C.c_int64, _dp, _dp, _dp,
                               C.c_double, C.c_uint64, C.c_uint64, C.c_double, _dp, _dp, _dp, _dp]),
+    "rvm_chain_record": (C.c_int, [C.c_int32, C.c_int32, _dp, C.c_int64, C.c_int64, C.c_int64, _dp, C.c_int64,
+                                   C.c_int64, _dp, _dp, _dp]),
+    "rvm_chain_moments": (C.c_int, [_dp, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _dp, _dp, _dp]),
+    "rvm_chain_autocov_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "rvm_chain_autocov": (C.c_int, [_dp, _dp, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _dp,
+                                    _dp, _dp]),
     "rvm_fd_params": (C.c_int, [C.c_int32, C.c_int32, _dp, C.c_double, _dp, _dp, _dp]),
     "rvm_logl_derivs_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rvm_logl_derivs": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int32, C.POINTER(C.c_int32), C.c_double, _dp, _dp,

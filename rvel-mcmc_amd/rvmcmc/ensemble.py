@@ -27,7 +27,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _lib, engine
+from . import _lib, chain, engine
 
 
 def _torch():
@@ -338,6 +338,16 @@ class EnsembleSampler:
             self.half_step(B, self.lnp[1], A, 1)
         self.iteration += 1
         engine.periodic_fault_check(self, self.plan)
+
+    def _chain_segments(self):
+        """Where this rank's walkers live, for chain.ChainRecorder: half 0, then half 1."""
+        if getattr(self, "pos", None) is None:
+            raise ValueError("set_positions first")
+        return [dict(x=self.pos[h], lnp=self.lnp[h], col0=0, n=self.nloc) for h in (0, 1)]
+
+    def run_mcmc(self, n_steps, recorder=None):
+        """n_steps iterations; every recorder.thin-th one goes into `recorder` (chain.ChainRecorder)."""
+        return chain.run_mcmc(self, n_steps, recorder)
 
     def check_faults(self):
         """Raise on level-split hand-off timeouts or NONFINITE log-likelihoods since the last check

@@ -17,7 +17,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib, engine
+from . import _lib, chain, engine
+from .chain import ChainRecorder
 from .ensemble import EnsembleSampler
 from .state import Encounter
 
@@ -292,6 +293,14 @@ class MhChains:
         self.iteration += 1
         engine.periodic_fault_check(self, self.plan)
 
+    def _chain_segments(self):
+        """The chains, for chain.ChainRecorder."""
+        return [dict(x=self.X, lnp=self.lnp, col0=0, n=self.n)]
+
+    def run_mcmc(self, n_steps, recorder=None):
+        """n_steps fused steps; every recorder.thin-th one goes into `recorder` (chain.ChainRecorder)."""
+        return chain.run_mcmc(self, n_steps, recorder)
+
     def check_faults(self):
         """rvm_plan_faults of the chains' plan: raises on hand-off timeouts / NONFINITE results."""
         self.last_faults = self.plan.check_faults(type(self).__name__)
@@ -302,4 +311,4 @@ from .smala import Alsmala, Smala, SmalaChains  # noqa: E402  (re-export with th
 from .tempering import PTSampler  # noqa: E402
 
 __all__ = ["Mcmc", "lnprob", "Ensemble", "Mh", "MhChains", "Smala", "Alsmala", "SmalaChains", "EnsembleSampler",
-           "PTSampler"]
+           "PTSampler", "ChainRecorder"]

@@ -21,7 +21,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib, engine
+from . import _lib, chain, engine
 
 # relative FD step and per-key absolute floors (h, k and l can be ~0)
 FD_REL_STEP = 1e-6
@@ -349,6 +349,14 @@ class SmalaChains:
         self.iteration += 1
         self._periodic_faults()
 
+
+    def _chain_segments(self):
+        """The chains and their cached logp, for chain.ChainRecorder."""
+        return [dict(x=self.X, lnp=self.cache["lp"], col0=0, n=self.n)]
+
+    def run_mcmc(self, n_steps, recorder=None):
+        """n_steps fused steps; every recorder.thin-th one goes into `recorder` (chain.ChainRecorder)."""
+        return chain.run_mcmc(self, n_steps, recorder)
 
     def _periodic_faults(self):  # (engine.periodic_fault_check over both plans)
         every = getattr(self, "fault_check_every", engine.FAULT_CHECK_EVERY)

@@ -44,7 +44,7 @@ import math
 
 import numpy as np
 
-from . import _lib, engine
+from . import _lib, chain, engine
 
 
 def _torch():
@@ -297,6 +297,17 @@ class PTSampler:
             self.nrecorded += 1
         self.iteration += 1
         engine.periodic_fault_check(self, self.plan)
+
+    def _chain_segments(self):
+        """The coldest temperature (beta = betas[0]) for chain.ChainRecorder: the first W/2 columns of
+        half 0, then of half 1 -- the walker order of positions()[0]."""
+        if self.pos is None:
+            raise ValueError("set_positions first")
+        return [dict(x=self.pos[h], lnp=self.lnp[h], col0=0, n=self.halfk) for h in (0, 1)]
+
+    def run_mcmc(self, n_steps, recorder=None):
+        """n_steps iterations; every recorder.thin-th one goes into `recorder` (chain.ChainRecorder)."""
+        return chain.run_mcmc(self, n_steps, recorder)
 
     def check_faults(self):
         """Raise on level-split hand-off timeouts, NONFINITE or UNRESOLVED log-likelihoods since the
