@@ -244,7 +244,7 @@ ORACLE_UNRESOLVED = 4
 
 def ext_multiplier(mult, rf_max):
     """The extension level's steps per base step (0: none): one more than the finest level, when
-    the plan refines at all and has room for one more level (RVM_MAX_LEVELS = 6; rvm_abi.hip --
+    the plan refines at all and has room for one more level (RVM_MAX_LEVELS = 6; rvm_plan_host.cpp --
     a plan whose stored levels would not fit its memory cap has none: rvm_plan_extension)."""
     m = [int(x) for x in mult]
     return max(m) + 1 if rf_max > 0 and 2 <= len(m) < 6 else 0

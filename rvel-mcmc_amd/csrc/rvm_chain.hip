@@ -10,6 +10,7 @@
 #include <math.h>
 
 #include "rvm_internal.h"
+#include "rvm_launch.h"
 
 namespace rvm {
 

@@ -19,6 +19,7 @@
 
 #include "rvm_hd.h"
 #include "rvm_internal.h"
+#include "rvm_launch.h"
 
 namespace rvm {
 

@@ -30,6 +30,7 @@
 // (The default -ffp-contract=fast fuses across statements depending on the surrounding code.)
 #pragma clang fp contract(on)
 
+#include "rvm_launch.h"
 #include "rvm_walker.h"
 
 // the main pass's drifts with the fifth-order Kepler guess (rvm_device.h drift G5; A/B knob, off:

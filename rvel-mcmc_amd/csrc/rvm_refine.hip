@@ -1,5 +1,6 @@
 // rvm_refine.hip -- dispatch of the refinement and eager kernels (rvm_refine_impl.h; instantiated per
 // planet count in rvm_refine_np<N>.hip) and the launch-generation bump.
+#include "rvm_launch.h"
 #include "rvm_refine_impl.h"
 
 namespace rvm {

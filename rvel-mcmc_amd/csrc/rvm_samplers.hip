@@ -12,6 +12,7 @@
 
 #include "rvm_device.h"
 #include "rvm_internal.h"
+#include "rvm_launch.h"
 #include "rvm_stretch.h"
 
 // No FMA contraction in the sampler arithmetic: proposals and accept tests are then bit-identical

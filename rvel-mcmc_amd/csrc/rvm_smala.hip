@@ -20,6 +20,7 @@
 
 #include "rvm_device.h"
 #include "rvm_internal.h"
+#include "rvm_launch.h"
 
 #pragma clang fp contract(off)
 

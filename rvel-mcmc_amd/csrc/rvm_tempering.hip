@@ -15,6 +15,7 @@
 
 #include "rvm_device.h"
 #include "rvm_internal.h"
+#include "rvm_launch.h"
 #include "rvm_stretch.h"
 
 // No FMA contraction (as rvm_samplers.hip): bit-identical to a plain IEEE restatement (numpy).
