@@ -20,6 +20,11 @@ derivatives, so the checks are:
     reference's integrator), whose adaptive steps make its finite differences noisier: 1e-4.
   * logp equals rvm_logl_batch's (T1 tier), the Hessian is symmetric, a sub-set of directions
     gives the sub-block, and non-OK walkers carry the likelihood kernel's status with NaN derivatives.
+
+Finite differences in double cannot see an error below their own noise (1e-6; 1e-3 for the order-2
+variations).  tests/test_gpu_derivs_exact.py (tier D0) holds the same kernel, in every instantiation,
+to a 60-digit restatement of the integrator (tests/wh_ref.py) within 3x the roundoff of a
+double-precision implementation (<= 1e-9 in the units above).
 """
 import numpy as np
 import pytest
