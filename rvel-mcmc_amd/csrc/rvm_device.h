@@ -139,7 +139,13 @@ __device__ __forceinline__ void stumpff23(double z, double& c2, double& c3) {
     c3 = b;
 }
 
-// Any |z|: quarter z until |z| <= 0.3, 8-term series, then the double-angle recurrences.
+// Any |z|: quarter z until |z| <= 0.3, 8-term series, then the double-angle recurrences for c2, c3
+// with c0 = 1 - z c2, c1 = 1 - z c3 formed anew at every level (Danby).  (Carrying c0, c1 through
+// their own recurrences, c0 <- 2 c0^2 - 1 and c1 <- c0 c1, multiplied c0's relative error by
+// 4 c0^2 / (2 c0^2 - 1) -- between 2 and 4 -- at every level: 56 u in c0 at z = -28 after four levels
+// against the 5 u the closed form attains in double; tier U0, tests/test_gpu_step_units.py.  For
+// z < 0 every term here is positive, and for z > 0 the cancellation in 1 - z c is an absolute error of
+// one rounding, small against c(-|z|).)
 __device__ __forceinline__ void stumpff_full(double z, double& c0, double& c1, double& c2, double& c3) {
     int n = 0;
     while (fabs(z) > 0.3 && n < 40) {  // rare: only for large steps / hyperbolic orbits
@@ -151,10 +157,11 @@ __device__ __forceinline__ void stumpff_full(double z, double& c0, double& c1, d
     double C1 = 1.0 - z * C3;
     double C0 = 1.0 - z * C2;
     for (; n > 0; n--) {
+        z *= 4.0;  // (exact)
         C3 = (C2 + C0 * C3) * 0.25;
         C2 = C1 * C1 * 0.5;
-        C1 = C0 * C1;
-        C0 = 2.0 * C0 * C0 - 1.0;
+        C1 = 1.0 - z * C3;
+        C0 = 1.0 - z * C2;
     }
     c0 = C0;
     c1 = C1;
