@@ -184,6 +184,16 @@ int rvm_plan_hedge_stats(rvm_plan* plan, int32_t reset, int64_t* hedged, int64_t
  * and the dependence on timing as rvm_plan_hedge_stats; all zero on a plan without a hedge.  Either pointer
  * may be NULL.  Synchronises the stream. */
 int rvm_plan_hedge_marks(rvm_plan* plan, int32_t reset, int64_t* marked, int64_t* gave_up, void* stream);
+/* Team A's wait for a running hedge block (after pass 1, when an open walker's hedge block
+ * has ranked its slots but not yet stored pass 2, team A polls for it before it hands the pass on to team B, and
+ * gives way when team B arrives; RVM_HEDGE_WAIT=0 at plan creation: never), since the last reset: waited = trials
+ * that polled, late_hits = polls that ended with the group finished from the hedge's results, gave_way = polls
+ * after which team A handed pass 2 on (team B arrived, the group's done word, a block that stopped, the safety
+ * bound, or results that did not end every walker); waited = late_hits + gave_way.  Reset semantics and the
+ * dependence on timing as rvm_plan_hedge_stats; all zero on a plan without a hedge and in the layouts without
+ * teams.  Any pointer may be NULL.  Synchronises the stream. */
+int rvm_plan_hedge_waits(rvm_plan* plan, int32_t reset, int64_t* waited, int64_t* late_hits, int64_t* gave_way,
+                         void* stream);
 /* Kernel timing (benchmarks): the plan's next max_launches likelihood evaluations (any entry point)
  * record HIP events on their stream around the likelihood kernel and around the refinement kernel
  * that follows it (0..4096; 0 stops).  rvm_plan_kernel_times waits for those events and returns

@@ -54,7 +54,8 @@ static void check_block(const std::vector<Range>& r, size_t block_bytes, const c
 static const char* const kKnobNames[] = {
     "RVM_SKIP_VARIANTS", "RVM_LATE_SPO",   "RVM_NO_LEVEL_SPLIT", "RVM_REFINE_TEAMS", "RVM_EAGER_SPLIT",
     "RVM_NO_EXTENSION",  "RVM_REFINE_SPLIT", "RVM_TEAMS_HINT",   "RVM_EAGER",        "RVM_EAGER_PASSES",
-    "RVM_HEDGE",         "RVM_HEDGE_GROUPS", "RVM_HEDGE_MARK",   "RVM_LS_F0"};
+    "RVM_HEDGE",         "RVM_HEDGE_GROUPS", "RVM_HEDGE_MARK",   "RVM_HEDGE_WAIT",
+    "RVM_LS_F0"};
 
 static rvm::PlanKnobs knobs_with(const char* name, const char* value) {
     setenv(name, value, 1);
@@ -72,13 +73,17 @@ static void check_plan_host(const rvm_config& cfg, const std::vector<double>& t,
     const PlanKnobs K = read_plan_knobs();
     expect(K.skip_variants == 1 && K.late_spo == 96.0 && !K.no_level_split && K.n_teams == RVM_TEAMS_DEFAULT &&
                K.eager_split == 1 && !K.no_extension && K.refine_split && K.teams_hint && K.eager &&
-               K.eager_passes == 1 && K.hedge_groups == RVM_HEDGE_GROUPS_MAX && K.hedge_mark == 1,
+               K.eager_passes == 1 && K.hedge_groups == RVM_HEDGE_GROUPS_MAX && K.hedge_mark == 1 &&
+               K.hedge_wait == 1,
            "knob defaults");
     expect(knobs_with("RVM_REFINE_TEAMS", "9").n_teams == RVM_TEAMS_MAX, "RVM_REFINE_TEAMS=9 clamps");
     expect(knobs_with("RVM_HEDGE", "0").hedge_groups == 0, "RVM_HEDGE=0");
     expect(knobs_with("RVM_HEDGE_GROUPS", "3").hedge_groups == 3, "RVM_HEDGE_GROUPS=3");
     expect(knobs_with("RVM_EAGER_PASSES", "2").eager_passes == 2, "RVM_EAGER_PASSES=2");
     expect(knobs_with("RVM_SKIP_VARIANTS", "0").skip_variants == 0, "RVM_SKIP_VARIANTS=0");
+    expect(knobs_with("RVM_HEDGE_WAIT", "0").hedge_wait == 0 && knobs_with("RVM_HEDGE_WAIT", "1").hedge_wait == 1 &&
+               knobs_with("RVM_HEDGE_WAIT", "2").hedge_wait == 2 && knobs_with("RVM_HEDGE_WAIT", "x").hedge_wait == 1,
+           "RVM_HEDGE_WAIT");
 
     int mult[RVM_MAX_LEVELS] = {}, max_mult = 0;
     expect(check_plan_config(&cfg, t.data(), rv.data(), sg.data(), n_obs, 4096, mult, &max_mult) == nullptr,
@@ -150,6 +155,11 @@ static void check_plan_host(const rvm_config& cfg, const std::vector<double>& t,
     expect(P.fin_level == 3, "fin_level");
     expect(P.ext_mult == 8 && P.mult[4] == 8 && P.inv_ext == 0.125 && P.inv_mult[4] == 0.125, "ext_mult");
     expect(P.rmax == 6 && P.rtol_dir == 2.5e-7 && P.cut == 1 && P.n_teams == RVM_TEAMS_DEFAULT, "adaptive scalars");
+    // team A's wait for a hedge block ends strictly before team B's wait for team A could
+    expect(P.hedge_wait_ticks == hedge_wait_bound(P.spin_ticks) && P.hedge_wait_ticks < (P.spin_ticks << 1),
+           "hedge_wait_ticks");
+    for (unsigned long long sp : {1ull, 2ull, 3ull, 4ull, 1000ull, 200000000ull, 1ull << 40, 1ull << 62})
+        expect(hedge_wait_bound(sp) < sp && hedge_wait_bound(sp) < (sp << 1), "hedge_wait_bound");
     for (int k = 0; k < 4; k++) {
         const double nh = 2.0 * M_PI * cfg.dt / (mult[k] * cfg.period_hint), zn = 2.0 * nh * nh;
         expect(P.nt[k] == (zn <= 0.1 ? 6 : (zn <= 0.3 ? 7 : 8)) && P.spec[k] == (zn <= 0.04 ? 1 : 0), "nt / spec");
@@ -193,10 +203,12 @@ static void check_plan_host(const rvm_config& cfg, const std::vector<double>& t,
             const RqLayout R = rq_layout(mw, teams);
             expect(R.xgroups == (int32_t)xg, "rq xgroups");
             check_block({{R.x, xg * nt * 256 * 8, true}, {R.xf, xg * nt * 2 * 8, true},
-                         {R.t, xg * (nt - 1) * 1024 * 8, true}, {R.tf, xg * nt * 8, true}, {R.c, 16 * w, true},
+                         {R.t, xg * (nt - 1) * 1024 * 8, true}, {R.tf, xg * nt * 8, true}, {R.tb, xg * 8, true},
+                         {R.c, 16 * w, true},
                          {R.w, 12 * w, false}, {R.n, 16, false}, {R.gen, 8, true}, {R.mark, 4 * w, false},
                          {R.depth, 8 * (RVM_DEPTH_WINDOW + 1), true}},
                         R.bytes, "rqmem layout");
+            expect(R.tb == R.tf + xg * nt * 8, "rq_tb right behind rq_tf");
             expect(R.gen == R.n + 32 && R.mark == R.n + 64 && R.mark % 64 == R.n % 64, "rq_n | gen_dev | rq_mark");
         }
         const HLayout H = h_layout((int32_t)em, mw);
@@ -204,6 +216,9 @@ static void check_plan_host(const rvm_config& cfg, const std::vector<double>& t,
         check_block({{H.hrv, 16 * em * hs, true}, {H.hsum, 48 * hs, true}, {H.hslot, 16 * hs, true},
                      {H.htab, 8 * w, true}, {H.hw, 8 * RVM_HW_WORDS, true}},
                     H.bytes, "hmem layout");
+        expect(RVM_HW_STATS + 5 <= RVM_HW_MARK && RVM_HW_MARK + 2 * RVM_HEDGE_GROUPS_MAX <= RVM_HW_WAIT &&
+                   RVM_HW_WAIT + 3 <= RVM_HW_WORDS,
+               "hw words");
         const ELayout E = e_layout((int32_t)em, mw);
         check_block({{E.rve, 32 * em * w, true}, {E.esum, 96 * w, true},
                      {E.eflag, 8 * (RVM_EFLAG_WORDS * (size_t)((RVM_EAGER_MAX + 15) / 16) + 8), true}},
@@ -249,6 +264,9 @@ int main() {
     expect(rvm_logl_batch(nullptr, 1, nullptr, 1.0, nullptr, nullptr, nullptr, nullptr) < 0, "logl null plan");
     int64_t mk = -1, gu = -1;
     expect(rvm_plan_hedge_marks(nullptr, 0, &mk, &gu, nullptr) < 0 && mk == -1 && gu == -1, "hedge_marks null plan");
+    int64_t lh = -1;
+    expect(rvm_plan_hedge_waits(nullptr, 0, &mk, &lh, &gu, nullptr) < 0 && mk == -1 && lh == -1 && gu == -1,
+           "hedge_waits null plan");
     rvm_param_map pm{};
     expect(rvm_stretch_half_step(nullptr, &pm, 10, 1, 0, nullptr, nullptr, nullptr, 1, nullptr, 2.0, 0, 0, 0, 1.0,
                                  nullptr, nullptr, nullptr, nullptr) < 0,

@@ -78,10 +78,15 @@ constexpr int RVM_HEDGE_MAX_W = 12288;
 // pass-2 walker-directions replayed, pass-2 walker-directions integrated although the launch hedged, [+ 3]
 // mark words written, [+ 4] hedge blocks that stopped on their mark (rvm_plan_hedge_marks);
 // then [RVM_HW_MARK + 2 g + d] group g direction d is not needed (generation << 8 | 1): none of its slots
-// is on the refinement kernel's lists in that direction
+// is on the refinement kernel's lists in that direction;
+// then [RVM_HW_WAIT ..] team A's waits for a running hedge block (rvm_plan_hedge_waits): trials that polled,
+// polls that ended in a commit, polls after which team A handed pass 2 on.
+// The completion word also takes generation << 8 | 3: the block has stopped (its mark, the cancel) and will
+// store no result
 constexpr int RVM_HW_STATS = 2 + 2 * RVM_HEDGE_GROUPS_MAX;
 constexpr int RVM_HW_MARK = RVM_HW_STATS + 3 + 3;
-constexpr int RVM_HW_WORDS = RVM_HW_MARK + 2 * RVM_HEDGE_GROUPS_MAX;
+constexpr int RVM_HW_WAIT = RVM_HW_MARK + 2 * RVM_HEDGE_GROUPS_MAX;
+constexpr int RVM_HW_WORDS = RVM_HW_WAIT + 3;
 
 // Epoch schedule of one integration direction (t >= 0 ascending from 0, or t < 0 descending).
 struct DirSched {
@@ -157,6 +162,10 @@ struct DevPlan {
     int32_t* rq_w;
     double* rq_c;
     int32_t rq_cap;
+    // (hedge; here and below in what was padding: the kernel argument keeps its size and every other field its
+    // offset) the bound of team A's wait for a running hedge block on the 100 MHz counter, strictly below the
+    // bound of team B's own wait (rvm_plan_host.h hedge_wait_bound)
+    uint32_t hedge_wait_ticks;
     // rq_mark [rq_cap]: the low 32 bits of the launch generation at each walker slot the likelihood
     // kernel listed -- a speculative iteration's half-1 variant whose partner was NOT listed has its
     // partner's decision final in StretchArgs::dec, so the variant the decision rules out is skipped
@@ -208,6 +217,11 @@ struct DevPlan {
     // 1: the refinement kernel marks, at its start, the hedge blocks whose group has no listed slot in their
     // direction, and they stop (RVM_HEDGE_MARK=0 at plan creation: they run until the cancel, A/B)
     int32_t hedge_mark;
+    // team A waits for a running hedge block before it hands pass 2 on (rvm_refine_impl.h hedge_wait_poll;
+    // RVM_HEDGE_WAIT: 0 never, 1 waits, 2 skips the first look so that every trial goes through the poll --
+    // tests).  Team B's arrival words, [rq_xgroups] (generation << 8 | 1: team B of the group is at its wait for
+    // team A's flag), lie behind rq_tf: rq_tf + rq_xgroups * n_teams
+    int32_t hedge_wait;
     double* hrv;
     double* hsum;
     unsigned long long* hslot;

@@ -186,6 +186,7 @@ void setup_side_features(rvm_plan* plan, const rvm::PlanKnobs& K) {
             P.hw = at<unsigned long long>(plan->hmem, L.hw);
             P.hedge_groups = K.hedge_groups;
             P.hedge_mark = K.hedge_mark;
+            P.hedge_wait = K.hedge_wait;
         }
     }
     if (!(refines && K.eager)) {
@@ -353,6 +354,17 @@ int rvm_plan_hedge_marks(rvm_plan* plan, int32_t reset, int64_t* marked, int64_t
     return 0;
 }
 
+int rvm_plan_hedge_waits(rvm_plan* plan, int32_t reset, int64_t* waited, int64_t* late_hits, int64_t* gave_way,
+                         void* stream) {
+    unsigned long long h[3];
+    const int rc = read_hw_words(plan, "rvm_plan_hedge_waits", rvm::RVM_HW_WAIT, 3, reset, stream, h);
+    if (rc != 0) return rc;
+    if (waited) *waited = (int64_t)h[0];
+    if (late_hits) *late_hits = (int64_t)h[1];
+    if (gave_way) *gave_way = (int64_t)h[2];
+    return 0;
+}
+
 int rvm_plan_faults(rvm_plan* plan, int32_t reset, int64_t* handoff_timeouts, int64_t* nonfinite,
                     int64_t* unresolved, int64_t* refined, int64_t* truncated, void* stream) {
     if (!plan) return fail(-1, "rvm_plan_faults: null plan");
@@ -404,6 +416,7 @@ int rvm_plan_set_handoff_timeout(rvm_plan* plan, double seconds) {
     if (!(seconds > 0.0) || !(seconds < 1e9)) return fail(-1, "rvm_plan_set_handoff_timeout: seconds out of range");
     const double ticks = seconds * 1e8;  // 100 MHz real-time counter
     plan->dev.spin_ticks = ticks < 1.0 ? 1ull : (unsigned long long)ticks;
+    plan->dev.hedge_wait_ticks = rvm::hedge_wait_bound(plan->dev.spin_ticks);
     return 0;
 }
 

@@ -43,6 +43,8 @@ PlanKnobs read_plan_knobs() {
     if (const char* hn = getenv("RVM_HEDGE_GROUPS"))
         K.hedge_groups = std::min(K.hedge_groups, std::max(0, std::min(atoi(hn), (int)RVM_HEDGE_GROUPS_MAX)));
     K.hedge_mark = starts(getenv("RVM_HEDGE_MARK"), '0') ? 0 : 1;
+    const char* hwt = getenv("RVM_HEDGE_WAIT");
+    K.hedge_wait = starts(hwt, '0') ? 0 : (starts(hwt, '2') ? 2 : 1);
     return K;
 }
 
@@ -187,6 +189,7 @@ void fill_plan_scalars(const rvm_config* cfg, const int* mult, int32_t n_obs, si
     P.rmax = P.rtol_dir < INFINITY ? cfg->resolve_max : 0;
     P.cut = 1;
     P.spin_ticks = 200000000ull;  // 2 s of the 100 MHz real-time counter without progress
+    P.hedge_wait_ticks = hedge_wait_bound(P.spin_ticks);
     // the LDS-coupled layouts' ring (DevPlan::lc_ring): up to RVM_LC_RING epochs, within
     // RVM_LC_RING_BYTES per group, at least 2 (a level runs at most a ring ahead of its combiner)
     const int emax = (int)std::max<size_t>(std::max(nf, nb), 1);
@@ -207,6 +210,11 @@ void fill_plan_scalars(const rvm_config* cfg, const int* mult, int32_t n_obs, si
     P.ext_spec = 0;
     P.inv_ext = 1.0;
     for (int k = 0; k <= RVM_MAX_LEVELS; k++) P.lw5[k] = 0.0;
+}
+
+uint32_t hedge_wait_bound(unsigned long long spin_ticks) {
+    const unsigned long long q = spin_ticks >> 2;  // (a 32-bit field: 42 s at the most)
+    return q < 0xFFFFFFFFull ? (uint32_t)q : 0xFFFFFFFFu;
 }
 
 bool plan_wants_extension(const DevPlan& P, const PlanKnobs& K) {
@@ -296,6 +304,7 @@ RqLayout rq_layout(int32_t max_walkers, int n_teams) {
     L.xf = take(L.bytes, xg * nt * 2 * u64);
     L.t = take(L.bytes, xg * (nt - 1) * 16 * 64 * u64);
     L.tf = take(L.bytes, xg * nt * u64);  // (+ the group's done word)
+    L.tb = take(L.bytes, xg * u64);       // (right behind rq_tf: team B has arrived, team A's wait gives way)
     L.c = take(L.bytes, 2 * (size_t)max_walkers * sizeof(double));
     // (rounded up to 8 bytes: an odd max_walkers left the 64-bit words after it, gen_dev and depth_w, 4 off)
     L.w = take(L.bytes, (3 * (size_t)max_walkers * sizeof(int32_t) + 7) & ~(size_t)7);

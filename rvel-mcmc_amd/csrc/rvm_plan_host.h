@@ -23,6 +23,7 @@ struct PlanKnobs {
     int32_t eager_passes;    // RVM_EAGER_PASSES: 1 or 2
     int32_t hedge_groups;    // RVM_HEDGE=0: no hedged pass 2; RVM_HEDGE_GROUPS caps its groups (0 .. RVM_HEDGE_GROUPS_MAX)
     int32_t hedge_mark;      // RVM_HEDGE_MARK: 0 leaves unneeded hedge blocks to the cancel
+    int32_t hedge_wait;      // RVM_HEDGE_WAIT: 0 team A never waits for a hedge block, 1 (default) it does, 2 it always polls
 };
 PlanKnobs read_plan_knobs();
 
@@ -50,6 +51,10 @@ inline int walkers_per_group(int n_planets) { return n_planets == 1 ? 64 : (n_pl
 // Every DevPlan field that is no device pointer and no DirSched, for a plan without extension (ext_mult 0)
 void fill_plan_scalars(const rvm_config* cfg, const int* mult, int32_t n_obs, size_t nf, size_t nb, int n_cu,
                        const PlanKnobs& K, DevPlan* P);
+// DevPlan::hedge_wait_ticks for a plan whose hand-off waits give up after spin_ticks: a quarter of it (42 s at
+// the most), so strictly below team B's own bound (spin_ticks << 1) for every spin_ticks >= 1 -- team A never
+// out-waits B
+uint32_t hedge_wait_bound(unsigned long long spin_ticks);
 bool plan_wants_extension(const DevPlan& P, const PlanKnobs& K);
 // the extension level's fields (ext_*, lw5, slot n_levels of mult / nt / spec / inv_mult), once its workspace exists
 void fill_plan_extension(DevPlan* P);
@@ -71,8 +76,8 @@ struct XLayout {  // lvx | rvp | rvp2 [n_teams - 1], each [2][emax][max_walkers]
     int32_t emax;
 };
 XLayout x_layout(size_t nf, size_t nb, int32_t max_walkers, int n_teams);
-struct RqLayout {  // rq_x | rq_xf | rq_t | rq_tf | rq_c | rq_w | rq_n [4] | gen_dev at + 32 | rq_mark at + 64 | depth_w
-    size_t x, xf, t, tf, c, w, n, gen, mark, depth, bytes;
+struct RqLayout {  // rq_x | rq_xf | rq_t | rq_tf | rq_tb | rq_c | rq_w | rq_n [4] | gen_dev at + 32 | rq_mark at + 64 | depth_w
+    size_t x, xf, t, tf, tb, c, w, n, gen, mark, depth, bytes;
     int32_t xgroups;  // exchange groups; each sized for max(n_teams, 2) teams
 };
 RqLayout rq_layout(int32_t max_walkers, int n_teams);

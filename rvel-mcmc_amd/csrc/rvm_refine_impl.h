@@ -88,8 +88,13 @@ namespace rvm {
 // integrated, [11] HW_REG_HW_ID, [12] cycles in the eager / team / split waits and replays,
 // [13..15] cycles from entry to: the list sizes read, the schedule staged, the walker state set up;
 // [16], [17] to the slot's walker index and stretch draws, and its parameter rows, loaded (this build
-// waits for each there).
-#define RVM_RPROF_SLOTS 20
+// waits for each there); [18] the real time of team A's look at the hedge after pass 1 (0: none), [19] that
+// look: the needed hedge blocks (2 group + direction) as a bit mask | open walker-directions without a hedge
+// index << 16 | took << 24 | every result complete at the look << 25 | the refinement group << 32, [20] the
+// open walker-directions per needed hedge block (4 bits each), [21] the real time a later team arrived at its
+// wait for the previous team's flag.  Hedge blocks: [4] stopped on its mark, [5] the real time its completion
+// word was stored (0: never).
+#define RVM_RPROF_SLOTS 24
 #define RVM_RPROF_MAX_WAVES 4096
 static __device__ unsigned long long rvm_rprof[RVM_RPROF_MAX_WAVES * RVM_RPROF_SLOTS];  // (per translation unit: rvm_refine_np2.hip reads it)
 #define RPROF_T(v) const unsigned long long v = __builtin_readcyclecounter()
@@ -151,6 +156,50 @@ __device__ __forceinline__ void hedge_mark_unneeded(const int32_t* rq_w, const i
         __hip_atomic_fetch_add(hw + RVM_HW_STATS + 3, nm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// (hedge) Team A's wait for the hedge blocks that are still running (refine_kernel<.., RVM_REFINE_HM>, wave 0,
+// after pass 1, before anything is published -- so team B cannot have taken this team's state, and the one
+// commit path stays the only one).  o0, o1: walker slot `lane`'s directions are open; wme: its walker slot.
+// A direction's hedge block is RUNNING when the slot's hedge index (htab) and the slot stored at it in that
+// direction (hslot, written by that direction's block after it has ranked the slots) carry this generation
+// and the block's completion word is neither 2 (complete) nor 3 (stopped).  Returns -1 at once, nothing
+// waited for, when some open direction has no running or complete block (no index: the block may never have
+// been dispatched; or it has stopped); else polls -- relaxed agent loads, s_sleep between them -- until
+// every needed word reads complete (returns 1; the caller's hedge_index then passes its acquire fence and
+// slot check), or a needed block reports that it has stopped, team B of the group has arrived at its wait for
+// this team's flag (*tbw), the group's done word is set, or P.hedge_wait_ticks have passed (returns 0: the
+// caller publishes as if it had not waited).  Team B's own wait is bounded by pass_ticks > hedge_wait_ticks
+// from its arrival, and this wait ends within one poll of that arrival.
+__device__ __forceinline__ int hedge_wait_poll(const DevPlan& P, const unsigned long long gen, const int wme,
+                                               const bool o0, const bool o1, const int wpb, const gu64* tbw,
+                                               const gu64* tdone) {
+    const unsigned long long done = (gen << 8) | 2ull, stop = (gen << 8) | 3ull;
+    // 0: not wanted or complete, 1: running, 2: nothing to wait for
+    auto state = [&](const int dd, const bool want) -> int {
+        if (!want) return 0;
+        const unsigned long long tb = __hip_atomic_load((gu64*)P.htab + wme, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int ix = (int)(tb & 0xFFFF);
+        if ((tb >> 16) != gen || ix >= RVM_HEDGE_STRIDE || ix / wpb >= RVM_HEDGE_GROUPS_MAX) return 2;
+        if (__hip_atomic_load((gu64*)P.hslot + (size_t)dd * RVM_HEDGE_STRIDE + ix, __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_AGENT) != ((gen << 16) | (unsigned long long)wme))
+            return 2;
+        const unsigned long long w =
+            __hip_atomic_load((gu64*)P.hw + 2 + 2 * (ix / wpb) + dd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return w == done ? 0 : (w == stop ? 2 : 1);
+    };
+    SpinClock clk;
+    clk.restart();
+    for (bool first = true;; first = false) {
+        const int s0 = state(0, o0), s1 = state(1, o1);
+        if (ballot(s0 == 2 || s1 == 2) != 0) return first ? -1 : 0;
+        if (ballot(s0 == 1 || s1 == 1) == 0) return 1;
+        const bool give = __hip_atomic_load(tbw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ((gen << 8) | 1ull) ||
+                          __hip_atomic_load(tdone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == done ||
+                          clk.expired(P.hedge_wait_ticks);
+        if (__builtin_amdgcn_readfirstlane((int)give)) return 0;  // (every lane the same exit)
+        __builtin_amdgcn_s_sleep(2);
+    }
+}
+
 // Bounded wait of a refinement pass's hand-off (split exchange, team B for team A): the partner
 // integrates a pass of 2^rf x the base steps without publishing progress, so the allowance scales
 // with the pass (a deep pass is no timeout; the timeout stays a last-resort fault)
@@ -175,9 +224,9 @@ struct DirState {
 // give every workgroup one direction anyway, where waves 4..7 of an 8-wave group only waited at the
 // barriers -- and a wave may then hold up to 512 registers (AGPRs too) instead of 256: no scratch
 // spill (round 5: 400 B per lane, 13.6 MB per steady-state launch; tests/test_kernel_resources.py).
-// NW = RVM_REFINE_HM (5): four waves, and the instantiation that marks the hedge blocks nobody can use (HM
-// below), launched for hedged launches of plans with DevPlan::hedge_mark.  The marking is compiled into that
-// instantiation alone: in the others it changed the register allocation of every launch's pass loops --
+// NW = RVM_REFINE_HM (5): four waves, and the instantiation of every hedged four-wave launch (HM below): it
+// marks the hedge blocks nobody can use (DevPlan::hedge_mark) and lets team A wait for a hedge block that is
+// still running (DevPlan::hedge_wait, hedge_wait_poll).  Both are compiled into that instantiation alone: in the others it changed the register allocation of every launch's pass loops --
 // launches without a hedge too (3 planets, 8192 walkers: +0.5 % per iteration).
 constexpr int RVM_REFINE_HM = 5;
 template <int NP, bool D3, int NW>
@@ -199,6 +248,7 @@ __global__ __launch_bounds__((NW == RVM_REFINE_HM ? 4 : NW) * 64) void refine_ke
     RPROF_RT(prt_entry);
 #ifdef RVM_PROFILE
     unsigned long long p_seg = 0, p_epo = 0, p_steps = 0, p_wait = 0, p_pass = 0;
+    unsigned long long p_look = 0, p_info = 0, p_need = 0, p_barr = 0;
     int p_lvl = -1;
 #endif
 
@@ -302,7 +352,7 @@ __global__ __launch_bounds__((NW == RVM_REFINE_HM ? 4 : NW) * 64) void refine_ke
         // A listed slot whose hedge index is not in yet (a block dispatched late) counts for nothing: its
         // group may stop, and the slot's pass 2 is integrated here as for any slot not hedged.
         if constexpr (HM) {
-            if (hedge && blockIdx.x == gridDim.x - 1 && wv == 0)
+            if (hedge && P.hedge_mark && blockIdx.x == gridDim.x - 1 && wv == 0)
                 hedge_mark_unneeded(P.rq_w, P.rq_cap, P.htab, P.hw, nq[0], nq[1], nq[2], gen, hedge, WPB);
         }
         leave();
@@ -924,6 +974,17 @@ __global__ __launch_bounds__((NW == RVM_REFINE_HM ? 4 : NW) * 64) void refine_ke
                 // a later team: the previous team's state after its pass (wave 0; the flag is in by now
                 // unless that team is late), then this pass's results for the walkers still open
                 if (wv == 0) {
+#ifdef RVM_PROFILE
+                    p_barr = __builtin_amdgcn_s_memrealtime();
+                    p_info |= (unsigned long long)g << 32;
+#endif
+                    // (hedge) team B is here with pass 2: a team A that waits for a hedge block gives way
+                    // (hedge_wait_poll), so this wait lasts one poll and the publish longer at most
+                    if constexpr (HM) {
+                        if (hedge && P.hedge_wait != 0 && tm == 1 && lane == 0)
+                            __hip_atomic_store((gu64*)(P.rq_tf + (size_t)P.rq_xgroups * P.n_teams + g), (gen << 8) | 1ull, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+                    }
                     SpinClock clk;
                     clk.restart();
                     unsigned long long f = 0;
@@ -1105,9 +1166,48 @@ __global__ __launch_bounds__((NW == RVM_REFINE_HM ? 4 : NW) * 64) void refine_ke
                     // split exchange has ordered the partner's) -- and if that ends every walker, take it:
                     // the group is done and team B stops.  Else nothing changes and team B goes on.
                     const bool o0 = live && s_open[0][lane] == 1, o1 = live && s_open[1][lane] == 1;
-                    const int hi[2] = {hedge_index(0, o0), hedge_index(1, o1)};
+                    int hi[2] = {hedge_index(0, o0), hedge_index(1, o1)};
                     bool took = false;
-                    if (ballot((o0 && hi[0] < 0) || (o1 && hi[1] < 0)) == 0) {
+                    bool allin = ballot((o0 && hi[0] < 0) || (o1 && hi[1] < 0)) == 0;
+#ifdef RVM_PROFILE
+                    // (timing build: when the look came, and which hedge blocks it needed)
+                    p_look = __builtin_amdgcn_s_memrealtime();
+                    p_info = (unsigned long long)g << 32;
+                    if (ballot((o0 && hi[0] < 0) || (o1 && hi[1] < 0)) == 0) p_info |= 1ull << 25;
+                    for (int d3 = 0; d3 < 2; d3++) {
+                        const bool want = d3 ? o1 : o0;
+                        const unsigned long long tb =
+                            __hip_atomic_load((gu64*)P.htab + wme, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        const int ix = (int)(tb & 0xFFFF);
+                        const bool tagged = (tb >> 16) == gen && ix < RVM_HEDGE_STRIDE && ix / WPB < RVM_HEDGE_GROUPS_MAX;
+                        const int blk = want && tagged ? 2 * (ix / WPB) + d3 : -1;
+                        for (int b = 0; b < 2 * RVM_HEDGE_GROUPS_MAX; b++) {
+                            const unsigned long long nb = __builtin_popcountll(ballot(blk == b));
+                            if (nb) {
+                                p_info |= 1ull << b;
+                                p_need += (nb < 15 ? nb : 15ull) << (4 * b);
+                            }
+                        }
+                        p_info += (unsigned long long)__builtin_popcountll(ballot(want && !tagged)) << 16;
+                    }
+#endif
+                    // (the wait, DevPlan::hedge_wait: a result that is not in yet but whose block is running is
+                    // polled for before anything is published, hedge_wait_poll; the trial and the commit below
+                    // are the same either way.  2: polled for even when the look found everything complete)
+                    int polled = -1;
+                    if constexpr (HM) {
+                        if (P.hedge_wait != 0 && (P.hedge_wait == 2 || !allin)) {
+                            polled = hedge_wait_poll(P, gen, wme, o0, o1, WPB, (const gu64*)(P.rq_tf + (size_t)P.rq_xgroups * P.n_teams + g), tdone);
+                            if (polled >= 0) {
+                                if (polled == 1) {
+                                    hi[0] = hedge_index(0, o0);
+                                    hi[1] = hedge_index(1, o1);
+                                }
+                                allin = polled == 1 && ballot((o0 && hi[0] < 0) || (o1 && hi[1] < 0)) == 0;
+                            }
+                        }
+                    }
+                    if (allin) {
                         DirState q[2] = {dir_load(0), dir_load(1)};
                         bool fl[2] = {false, false};
                         for (int d3 = 0; d3 < 2; d3++) {
@@ -1171,7 +1271,19 @@ __global__ __launch_bounds__((NW == RVM_REFINE_HM ? 4 : NW) * 64) void refine_ke
                         if (took) __hip_atomic_fetch_add(P.counters + 3, nd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         __hip_atomic_fetch_add((gu64*)P.hw + RVM_HW_STATS + (took ? 1 : 2), nd, __ATOMIC_RELAXED,
                                                __HIP_MEMORY_SCOPE_AGENT);
+                        if constexpr (HM) {
+                            // (a trial that polled: it ended in this commit, or pass 2 goes on to team B)
+                            if (polled >= 0) {
+                                __hip_atomic_fetch_add((gu64*)P.hw + RVM_HW_WAIT, 1ull, __ATOMIC_RELAXED,
+                                                       __HIP_MEMORY_SCOPE_AGENT);
+                                __hip_atomic_fetch_add((gu64*)P.hw + RVM_HW_WAIT + (took ? 1 : 2), 1ull, __ATOMIC_RELAXED,
+                                                       __HIP_MEMORY_SCOPE_AGENT);
+                            }
+                        }
                     }
+#ifdef RVM_PROFILE
+                    if (took) p_info |= 1ull << 24;
+#endif
                     if (took) m0 = m1 = 0;
                 }
                 if (lane == 0) {
@@ -1271,6 +1383,10 @@ __global__ __launch_bounds__((NW == RVM_REFINE_HM ? 4 : NW) * 64) void refine_ke
             o[15] = pt_setup - pt_entry;
             o[16] = pt_slot - pt_entry;
             o[17] = pt_rows - pt_entry;
+            o[18] = p_look;
+            o[19] = p_info;
+            o[20] = p_need;
+            o[21] = p_barr;
         }
 #endif
     }
@@ -1472,10 +1588,14 @@ __global__ __launch_bounds__(256) void hedge_kernel(const DevPlan P, const int W
         s_cancel[0] = stopped();
     }
     __syncthreads();
-    // (a block that stops on its mark is counted: hw[RVM_HW_STATS + 4], rvm_plan_hedge_marks)
+    // (a block that stops on its mark is counted: hw[RVM_HW_STATS + 4], rvm_plan_hedge_marks; and a block
+    // that stops says so in its completion word, code 3: a team A that polls for its result counts a miss at
+    // once instead of waiting for team B, hedge_wait_poll)
     auto count_marked = [&]() {
-        if (tid == 0 && s_marked)
-            __hip_atomic_fetch_add(hw + RVM_HW_STATS + 4, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) {
+            if (s_marked) __hip_atomic_fetch_add(hw + RVM_HW_STATS + 4, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(hw + 2 + 2 * g + dd, (gen << 8) | 3ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     };
     if (s_cancel[0]) {  // (before the slots are read)
         count_marked();
@@ -1486,26 +1606,63 @@ __global__ __launch_bounds__(256) void hedge_kernel(const DevPlan P, const int W
         s_ck[i] = kbad;
         s_ci[i] = 0;
     }
-    // every slot's key from its proposal rows (the refinement prologue's own code)
-    for (int i = tid; i < W; i += 256) {
-        int kind = 0, wk = i, jst = 0, jp = 0;
-        double zst = 0.0, zp = 0.0;
-        stretch_slot(sa, i, kind, wk, zst, jst, zp, jp);
-        double sc = INFINITY;
-        bool ok = true;
+    // every slot's key from its proposal rows (the refinement prologue's values, walker_param's stretch
+    // branch expression for expression).  A thread has W / 256 slots, and a slot's row addresses depend on its
+    // Philox draw: one slot after the other that was W / 256 rounds of dependent loads before the first
+    // step (24 at 6144 slots; entry to first step 151 us).  So KCH slots at a
+    // time: their draws, then every row's loads -- addresses by select, not by branch, so that none waits for
+    // another: c or c0 at j, c at the partner's j (kind 2; slot 0's row otherwise, not used), x or x1 -- then
+    // the keys.
+    constexpr int KCH = NP <= 2 ? 4 : 2;
+    for (int i0 = tid; i0 < W; i0 += 256 * KCH) {
+        int kind[KCH], wk[KCH], jst[KCH], jp[KCH];
+        double zst[KCH], zp[KCH];
 #pragma unroll
-        for (int p = 0; p < NP; p++) {
-            const double m = walker_param(true, nullptr, W, wk, sa, PR * p + 0, zst, jst, kind, zp, jp);
-            const double a = walker_param(true, nullptr, W, wk, sa, PR * p + 1, zst, jst, kind, zp, jp);
-            const double h = walker_param(true, nullptr, W, wk, sa, PR * p + 2, zst, jst, kind, zp, jp);
-            const double k = walker_param(true, nullptr, W, wk, sa, PR * p + 3, zst, jst, kind, zp, jp);
-            const double e = sqrt(h * h + k * k);
-            // (walker_setup's prior bounds: a slot outside them is never refined)
-            ok = ok && a > 0.02 && m > 5e-6 && e < 1.0;
-            sc = fmin(sc, a * (1.0 - e) / cbrt(1.0 + m));
+        for (int c = 0; c < KCH; c++) {
+            const int i = i0 + 256 * c < W ? i0 + 256 * c : i0;  // (past the last slot: the chunk's first again)
+            kind[c] = 0, wk[c] = i, jst[c] = 0, jp[c] = 0;
+            zst[c] = 0.0, zp[c] = 0.0;
+            stretch_slot(sa, i, kind[c], wk[c], zst[c], jst[c], zp[c], jp[c]);
         }
-        ok = ok && isfinite(sc) && sc > 0.0;
-        s_key[i] = ok ? (unsigned long long)__double_as_longlong(sc) : kbad;
+        double va[KCH][4 * NP], vb[KCH][4 * NP], vx[KCH][4 * NP];
+#pragma unroll
+        for (int c = 0; c < KCH; c++) {
+#pragma unroll
+            for (int q = 0; q < 4 * NP; q++) {
+                const int k = sa.src[PR * (q >> 2) + (q & 3)];
+                const int ku = k < 0 ? 0 : k;
+                // (kinds 1 and 2 only with n_spec > 0, where c0 and x1 are set; a hedged launch is a stretch
+                // launch: sa.c is set, no MH step, no stencil)
+                const double* ba = kind[c] == 0 ? sa.c : sa.c0;
+                const double* bx = kind[c] == 0 ? sa.x : sa.x1;
+                const size_t sx = (size_t)(kind[c] == 0 ? sa.xstride : sa.n_spec);
+                va[c][q] = ba[(size_t)jst[c] * sa.dim + ku];
+                vb[c][q] = sa.c[(size_t)(kind[c] == 2 ? jp[c] : 0) * sa.dim + ku];
+                vx[c][q] = bx[(size_t)ku * sx + wk[c]];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < KCH; c++) {
+            double row[4 * NP];
+#pragma unroll
+            for (int q = 0; q < 4 * NP; q++) {
+                const int r = PR * (q >> 2) + (q & 3);
+                const double cj = kind[c] == 2 ? stretch_q(vb[c][q], zp[c], va[c][q]) : va[c][q];
+                row[q] = sa.src[r] < 0 ? sa.base[r] : stretch_q(cj, zst[c], vx[c][q]);
+            }
+            double sc = INFINITY;
+            bool ok = true;
+#pragma unroll
+            for (int p = 0; p < NP; p++) {
+                const double m = row[4 * p + 0], a = row[4 * p + 1], h = row[4 * p + 2], k = row[4 * p + 3];
+                const double e = sqrt(h * h + k * k);
+                // (walker_setup's prior bounds: a slot outside them is never refined)
+                ok = ok && a > 0.02 && m > 5e-6 && e < 1.0;
+                sc = fmin(sc, a * (1.0 - e) / cbrt(1.0 + m));
+            }
+            ok = ok && isfinite(sc) && sc > 0.0;
+            if (i0 + 256 * c < W) s_key[i0 + 256 * c] = ok ? (unsigned long long)__double_as_longlong(sc) : kbad;
+        }
     }
     // four bins per lane of wave 0: the exclusive prefix sums of c[0..255] in place
     auto scan256 = [&](int* c) {
@@ -1702,6 +1859,7 @@ __global__ __launch_bounds__(256) void hedge_kernel(const DevPlan P, const int W
         o[9] = (unsigned long long)blockIdx.x | (1ull << 29) | ((unsigned long long)(cancelled ? 1 : 0) << 30);
         o[10] = cancelled ? 0 : 1;
         o[11] = (unsigned long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_REG_HW_ID
+        o[4] = (unsigned long long)s_marked;
     }
 #endif
     if (cancelled) {
@@ -1728,6 +1886,11 @@ __global__ __launch_bounds__(256) void hedge_kernel(const DevPlan P, const int W
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0)
             __hip_atomic_store(hw + 2 + 2 * g + dd, (gen << 8) | 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#ifdef RVM_PROFILE
+        if (lane == 0 && RVM_RPROF_MAX_WAVES / 2 + (size_t)blockIdx.x * 8 < RVM_RPROF_MAX_WAVES)
+            rvm_rprof[(RVM_RPROF_MAX_WAVES / 2 + (size_t)blockIdx.x * 8) * RVM_RPROF_SLOTS + 5] =
+                __builtin_amdgcn_s_memrealtime();
+#endif
     }
 }
 
@@ -1833,8 +1996,9 @@ static hipError_t launch_refine_t(const DevPlan& P, int W, const double* params,
     const int groups = (W + wpb - 1) / wpb + 2;
     int nb = std::max(2, std::min(P.n_cu > 0 ? P.n_cu : 256, 2 * groups));
     nb &= ~1;
-    // (a hedged launch of a plan that marks the unneeded hedge blocks: the kernel with the marking compiled in)
-    if (w4 && hedge && P.hedge_mark && smem <= refine_budget<NPV, D3V, RVM_REFINE_HM>())
+    // (a hedged launch: the kernel with the marking of unneeded hedge blocks and team A's wait for running ones
+    // compiled in, each behind its flag -- DevPlan::hedge_mark, hedge_wait)
+    if (w4 && hedge && smem <= refine_budget<NPV, D3V, RVM_REFINE_HM>())
         refine_kernel<NPV, D3V, RVM_REFINE_HM><<<dim3(nb), dim3(256), smem, stream>>>(P, W, params, hill_factor, rv_out,
                                                                                       logl, status, sa, eager, hedge);
     else if (w4)
@@ -1853,7 +2017,7 @@ static hipError_t prepare_refine_t(const DevPlan& P) {
     const size_t smem = (size_t)emax * 8 * sizeof(double);
     const size_t b = std::min(refine_budget<NPV, D3V, 4>(), refine_budget<NPV, D3V, 8>());
     if (P.hedge_groups > 0) (void)hedge_budget<NPV, D3V>();  // (the hedge kernel's LDS attribute, set here once)
-    if (P.hedge_groups > 0 && P.hedge_mark) (void)refine_budget<NPV, D3V, RVM_REFINE_HM>();  // (the marking instantiation's)
+    if (P.hedge_groups > 0) (void)refine_budget<NPV, D3V, RVM_REFINE_HM>();  // (the hedged instantiation's)
     return smem <= b ? hipSuccess : hipErrorInvalidConfiguration;
 }
 

@@ -241,6 +241,15 @@ class LoglPlan:
                                                  _lib.stream_handle(stream)), "rvm_plan_hedge_marks")
         return dict(marked=m.value, gave_up=g.value)
 
+    def hedge_waits(self, reset=False, stream=None) -> dict:
+        """rvm_plan_hedge_waits (synchronises the stream): trials of team A that polled for a running hedge
+        block, polls that ended with the group finished from the hedge, and polls after which pass 2 was
+        handed on to team B (waited = late_hits + gave_way).  Timing-dependent, as hedge_stats()."""
+        w, h, g = C.c_int64(), C.c_int64(), C.c_int64()
+        _lib.check(self.lib.rvm_plan_hedge_waits(self._h, int(bool(reset)), C.byref(w), C.byref(h), C.byref(g),
+                                                 _lib.stream_handle(stream)), "rvm_plan_hedge_waits")
+        return dict(waited=w.value, late_hits=h.value, gave_way=g.value)
+
     def check_faults(self, what="plan", stream=None, group=None) -> dict:
         """Raise RvmError on hand-off timeouts, NONFINITE results, or (a plan that refines, resolve_max
         > 0) UNRESOLVED results since the last check: emcee raises on a NaN log-probability

@@ -19,7 +19,7 @@ import torch  # noqa: E402
 from conftest import S2_PLANETS  # noqa: E402
 from rvmcmc import _lib, engine  # noqa: E402
 
-SLOTS, MAXW = 20, 4096
+SLOTS, MAXW = 24, 4096
 
 
 def main():

@@ -51,7 +51,10 @@ def run(resolve_tol, levels=(4, 5, 6, 7), resolve_max=None, iters=int(os.environ
                 lib=os.environ.get("RVM_LIB_PATH", "default"),
                 # (the hedged pass 2's statistics over warm-up and timed iterations; a library without it: None)
                 hedge=ens.plan.hedge_stats() if hasattr(ens.plan, "hedge_stats") else None,
-                hedge_env={k: os.environ.get(k) for k in ("RVM_HEDGE", "RVM_HEDGE_GROUPS", "RVM_REFINE_TEAMS")})
+                # (team A's waits for running hedge blocks, over the same iterations)
+                hedge_waits=ens.plan.hedge_waits() if hasattr(ens.plan, "hedge_waits") else None,
+                hedge_env={k: os.environ.get(k) for k in ("RVM_HEDGE", "RVM_HEDGE_GROUPS", "RVM_REFINE_TEAMS",
+                                                          "RVM_HEDGE_WAIT")})
 
 
 if __name__ == "__main__":
