@@ -59,23 +59,10 @@
 
 #include "rvm_walker.h"
 
-// the halving passes' Kepler guess (rvm_device.h drift KG): 0 the fourth-order guess, 1 the fifth-order
-// one (G5).  G5 on every step
-// cuts a lone wave's step on eccentric orbits at coarse resolution (933 -> 693 cycles at 32 steps per
-// inner orbit, e = 0.22) but costs ~55 cycles where the fourth-order guess already takes one Halley
-// step (scripts/probe/seg_bench.hip, profiles/r05g_seg_bench_g5.txt); at the passes' finer steps the
-// latter dominates: steady state 1.388 ms per iteration and config 4 318k chain-steps/s with the
-// fourth-order guess against 1.422 / 295k with G5 (profiles/r05h_steady_ab_refine_g5.jsonl,
-// r05h_config4_ab_refine_g5.jsonl; "default" there is G5 on).  The refinement and eager kernels share
-// the setting: their bits must agree.
-#ifndef RVM_REFINE_GUESS
-#define RVM_REFINE_GUESS 0
-#endif
-// the blocks' count of list-size readers (the last one resets the lists): relaxed after the reads
-// have returned (1), or acquire-release (0: an agent-scope L2 writeback before, invalidate after)
-#ifndef RVM_REFINE_RELAXED_COUNT
-#define RVM_REFINE_RELAXED_COUNT 0
-#endif
+// The halving passes integrate with the fourth-order Kepler guess (segment_gated's default, KG = 0): the
+// fifth-order one on every step measured 1.422 ms per steady-state iteration against 1.388, and 295k
+// against 318k chain-steps/s on config 4 (profiles/r05h_steady_ab_refine_g5.jsonl,
+// r05h_config4_ab_refine_g5.jsonl) -- it saves a Halley step only at coarse resolution.
 
 namespace rvm {
 
@@ -218,6 +205,23 @@ struct DirState {
     double chi, lb, pest, best, bchi;
 };
 
+// The Richardson combiner of one epoch for one walker: from the levels' star vx (lv[q * 64], level q's value
+// in the LDS row of this lane) the extrapolated RV, the RV without the coarsest level, and the epoch's
+// terms of chi2 and of the extrapolation-error estimate against the observation ob of variance s2.
+// side_pass's; refine_kernel's epoch loop still writes these expressions out itself, because its register
+// allocation is pinned by a test and this call moved it -- a change to one
+// is a change to both.
+__device__ __forceinline__ void combine_epoch(const DevPlan& P, const int nl, const double* lv, const double ob,
+                                              const double s2, double& rvx, double& rv3, double& dc2, double& de2) {
+    rvx = 0.0;
+    rv3 = 0.0;
+    for (int q = 0; q < nl; q++) rvx += P.lw[q] * lv[q * 64];
+    for (int q = 1; q < nl; q++) rv3 += P.lw3[q] * lv[q * 64];
+    const double r = rvx - ob;
+    dc2 = (r * r) / s2;
+    de2 = fabs((rvx - rv3) * (r + (rv3 - ob))) / s2;
+}
+
 // NW: waves per workgroup.  8 (512 threads) runs a both-direction group's two directions side by side
 // (mirrored levels) and plans of up to 8 levels; 4 (256 threads, plans of at most four levels) runs
 // them one after the other when a group holds both -- the split and team layouts, the steady state's,
@@ -278,14 +282,7 @@ __global__ __launch_bounds__((NW == RVM_REFINE_HM ? 4 : NW) * 64) void refine_ke
                     d = (int)(v[i] & 0xFF);
         }
         s_depth = d;
-#if RVM_REFINE_RELAXED_COUNT
-        // (the three loads have returned before the count is bumped: the last block's reset
-        // cannot overtake them; no release / acquire -- an L2 writeback and invalidate -- needed)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int done = __hip_atomic_fetch_add(P.rq_n + 3, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
         const int done = __hip_atomic_fetch_add(P.rq_n + 3, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-#endif
         if (done == (int)gridDim.x - 1) {
             for (int i = 0; i < 4; i++) __hip_atomic_store(P.rq_n + i, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (!eager && !hedge) __hip_atomic_store(P.gen_dev, g0 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -805,10 +802,10 @@ __global__ __launch_bounds__((NW == RVM_REFINE_HM ? 4 : NW) * 64) void refine_ke
                         // (a later team's first pass stops part-way once an earlier team has finished the
                         // group: the barrier below then breaks every wave out at this epoch)
                         if (bfirst)
-                            (void)segment_gated_c<D3, NP, L, RVM_REFINE_GUESS>(s, kq, r_len[e] * sc, ns, nt_r, tdone,
+                            (void)segment_gated_c<D3, NP, L>(s, kq, r_len[e] * sc, ns, nt_r, tdone,
                                                                                  nullptr, (gen << 8) | 2ull, late);
                         else
-                            segment_gated<D3, NP, L, RVM_REFINE_GUESS>(s, kq, r_len[e] * sc, ns, nt_r, late);
+                            segment_gated<D3, NP, L>(s, kq, r_len[e] * sc, ns, nt_r, late);
                     }
                     RPROF_T(pt_s1);
 #ifdef RVM_PROFILE
@@ -1393,6 +1390,90 @@ __global__ __launch_bounds__((NW == RVM_REFINE_HM ? 4 : NW) * 64) void refine_ke
     leave();
 }
 
+// A halving pass run beside the likelihood launch (eager_kernel, hedge_kernel): a block of four waves, one
+// per level, integrates pass rf of one direction (SR) for its up to WPB walker slots, whose state at t = 0
+// is in `s`.  Level 0's lanes with `mine` set (lane = walker slot) combine: they store the RV per epoch
+// write-through at rvo + e * stride, and at the end chi2, the estimate and the encounter flag at
+// es, es + stride, es + 2 stride; wave 0 drains its stores and then sets the completion word *done to
+// generation << 8 | 2 -- the layout the refinement kernel replays (its eager and hedge replays, pass_result).
+// stop(): the block's cancel test, called by wave 0's lane 0 at every epoch; every wave leaves at the
+// barrier of the epoch that sees it.  SEGC: segments are cancellable part-way too (segment_gated_c on
+// the word cw reaching ctag); a wave stopped inside the last segment holds a partial state, so wave 0 then
+// calls stop() once more, after the barrier, before anything is published.
+// Returns 0 when the pass ran to its end (wave 0 has published), 1 (every wave) when an epoch's test
+// stopped it, 2 (wave 0) when the test before publishing did.
+struct SidePassLds {
+    double rv[2][RVM_MAX_LEVELS][64];  // the levels' star vx per epoch, double-buffered
+    int enc[RVM_MAX_LEVELS][64];       // their encounter flags
+    int cancel[2];                     // the cancel test, by epoch parity
+};
+template <int NP, bool D3, bool SEGC, typename Stop>
+__device__ __forceinline__ int side_pass(const DevPlan& P, const DirSched& SR, Lane<NP>& s, const int rf,
+                                         const bool mine, gu64* rvo, gu64* es, const size_t stride, gu64* done,
+                                         const unsigned long long gen, const gu64* cw, const unsigned long long ctag,
+                                         SidePassLds& m, Stop stop) {
+    constexpr int L = LanesPerWalker<NP>::value;
+    const int wv = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int slot = lane / L;
+    const int pl_idx = lane % L;
+    const int nl = P.n_levels;
+    const int Er = SR.n_epochs;
+    int k = wv < nl ? wv : -1;
+    k = __builtin_amdgcn_readfirstlane(k);
+    const int k_u = k < 0 ? 0 : k;
+    const bool work = k >= 0;
+    KickPrep<NP> kq{};
+    if (work && Er > 0) kq = kick_prep<NP, L, D3>(s, 1.875);
+    const int m_r = P.mult[k_u] << rf;
+    const int nt_r = P.nt[k_u];
+    const bool late = P.late_mult > 0 && m_r >= P.late_mult;  // (the late vote: the same bits)
+    const double sc = ldexp(P.inv_mult[k_u], -rf);
+    const bool cmb = work && k == 0 && mine;
+    double c2 = 0.0, e2 = 0.0;
+    for (int e = 0; e < Er; e++) {
+        const int ns = __builtin_amdgcn_readfirstlane(work ? SR.seg_n[e] * m_r : 0);
+        if (ns > 0) {
+            if constexpr (SEGC)
+                (void)segment_gated_c<D3, NP, L>(s, kq, SR.seg_h1[e] * sc, ns, nt_r, cw, nullptr, ctag, late);
+            else
+                segment_gated<D3, NP, L>(s, kq, SR.seg_h1[e] * sc, ns, nt_r, late);
+        }
+        if (work) {
+            const double v0 = star_vx<NP, L>(s);
+            if (pl_idx == 0) m.rv[e & 1][k_u][slot] = v0;
+        }
+        if (wv == 0 && lane == 0) m.cancel[e & 1] = stop();
+        __syncthreads();
+        if (m.cancel[e & 1]) return 1;
+        if (cmb) {
+            double rvx, rv3, dc2, de2;
+            combine_epoch(P, nl, &m.rv[e & 1][0][lane], SR.obs_rv[e], SR.obs_s2[e], rvx, rv3, dc2, de2);
+            c2 += dc2;
+            e2 += de2;
+            __hip_atomic_store(rvo + (size_t)e * stride, (unsigned long long)__double_as_longlong(rvx), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    if (work && pl_idx == 0) m.enc[k_u][slot] = (int)(((s.encm >> lane) & kick_enc_bits<NP>()) != 0);
+    __syncthreads();
+    if (wv != 0) return 0;
+    if constexpr (SEGC) {
+        if (__builtin_amdgcn_readfirstlane((int)stop())) return 2;
+    }
+    if (cmb) {
+        int er = 0;
+        for (int q = 0; q < nl; q++) er |= m.enc[q][lane];
+        auto bits = [](double v) { return (unsigned long long)__double_as_longlong(v); };
+        __hip_atomic_store(es, bits(c2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(es + stride, bits(e2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(es + 2 * stride, bits((double)er), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (lane == 0) __hip_atomic_store(done, (gen << 8) | 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return 0;
+}
+
 // Eager halving passes (round 4): for a plain launch of 32..512 walkers (SMALA's centres, batched
 // State evaluations), halving pass 1 (and 2 with RVM_EAGER_PASSES=2) of EVERY walker runs on the
 // plan's side stream at the same time as the likelihood kernel, on CUs the launch leaves idle.
@@ -1414,18 +1495,12 @@ __global__ __launch_bounds__(256) void eager_kernel(const DevPlan P, const int W
     constexpr int WPB = 64 / L;
     constexpr int PR = D3 ? 7 : 5;
     constexpr int R = PR * NP;
-    const int wv = threadIdx.x >> 6;
     const int lane = threadIdx.x & 63;
     const int slot = lane / L;
     const int pl_idx = lane % L;
-    const int nl = P.n_levels;
     const int np2 = P.eager_passes == 2;  // (blocks per group: 2 directions x eager_passes)
     const int g = blockIdx.x >> (1 + np2), dd = (blockIdx.x >> np2) & 1, rf = 1 + (np2 & blockIdx.x);
-    const DirSched& SR = dd ? P.bwd : P.fwd;
-    const int Er = SR.n_epochs;
-    __shared__ double s_rv[2][RVM_MAX_LEVELS][64];
-    __shared__ int s_enc[RVM_MAX_LEVELS][64];
-    __shared__ int s_cancel[2];
+    __shared__ SidePassLds s_sp;
     __shared__ unsigned long long s_gen;
     gu64* ef = (gu64*)(P.eflag + (size_t)g * RVM_EFLAG_WORDS);
     if (threadIdx.x == 0) s_gen = __hip_atomic_load(P.gen_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1437,9 +1512,9 @@ __global__ __launch_bounds__(256) void eager_kernel(const DevPlan P, const int W
                __hip_atomic_load(ef + 6 + dd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ctag;
     };
     gu64* item = ef + 2 + 2 * (rf - 1) + dd;
-    if (threadIdx.x == 0) s_cancel[0] = cancelled_now() || !claim_item(item, gen, 1ull);
+    if (threadIdx.x == 0) s_sp.cancel[0] = cancelled_now() || !claim_item(item, gen, 1ull);
     __syncthreads();
-    if (s_cancel[0]) return;  // (before the walkers are read)
+    if (s_sp.cancel[0]) return;  // (before the walkers are read)
     const int w0 = g * WPB;
     const int wo = w0 + slot < W ? w0 + slot : w0;  // (lanes past the last walker repeat the group's first)
     double rowv[R];
@@ -1449,66 +1524,15 @@ __global__ __launch_bounds__(256) void eager_kernel(const DevPlan P, const int W
     int status = RVM_STATUS_OK;
     double e2w;
     walker_setup<NP, D3, L>(rowv, pl_idx, hill_factor, s, status, e2w);
-    int k = wv < nl ? wv : -1;
-    k = __builtin_amdgcn_readfirstlane(k);
-    const int k_u = k < 0 ? 0 : k;
-    const bool work = k >= 0;
-    KickPrep<NP> kq{};
-    if (work && Er > 0) kq = kick_prep<NP, L, D3>(s, 1.875);
-    const int m_r = P.mult[k_u] << rf;
-    const int nt_r = P.nt[k_u];
-    const bool late = P.late_mult > 0 && m_r >= P.late_mult;  // (the late vote: the same bits)
-    const double sc = ldexp(P.inv_mult[k_u], -rf);
-    const bool cmb = work && k == 0 && lane < WPB && w0 + lane < W;
+    const bool mine = lane < WPB && w0 + lane < W;
     const size_t plane = (size_t)P.lvx_emax * P.lvx_stride;
-    gu64* rvo = (gu64*)(P.rve + ((size_t)(rf - 1) * 2 + dd) * plane + (cmb ? w0 + lane : 0));
-    double c2 = 0.0, e2 = 0.0;
-    bool cancelled = false;
-    for (int e = 0; e < Er; e++) {
-        const int ns = __builtin_amdgcn_readfirstlane(work ? SR.seg_n[e] * m_r : 0);
-        // (cancels are seen at the epochs: the segment-level cancel of team B's passes,
-        // segment_gated_c, measured slower here -- config 4 0.645 -> 0.66 ms median step,
-        // profiles/r05r_config4_ab_cancel.jsonl)
-        if (ns > 0) segment_gated<D3, NP, L, RVM_REFINE_GUESS>(s, kq, SR.seg_h1[e] * sc, ns, nt_r, late);
-        if (work) {
-            const double v0 = star_vx<NP, L>(s);
-            if (pl_idx == 0) s_rv[e & 1][k_u][slot] = v0;
-        }
-        if (wv == 0 && lane == 0) s_cancel[e & 1] = cancelled_now();
-        __syncthreads();
-        if (s_cancel[e & 1]) {
-            cancelled = true;
-            break;
-        }
-        if (cmb) {  // (the refinement kernel's combiner, expression for expression)
-            double rvx = 0.0, rv3 = 0.0;
-            for (int q = 0; q < nl; q++) rvx += P.lw[q] * s_rv[e & 1][q][lane];
-            for (int q = 1; q < nl; q++) rv3 += P.lw3[q] * s_rv[e & 1][q][lane];
-            const double ob = SR.obs_rv[e], s2 = SR.obs_s2[e];
-            const double r = rvx - ob;
-            c2 += (r * r) / s2;
-            e2 += fabs((rvx - rv3) * (r + (rv3 - ob))) / s2;
-            __hip_atomic_store(rvo + (size_t)e * P.lvx_stride, (unsigned long long)__double_as_longlong(rvx),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    if (cancelled) return;
-    if (work && pl_idx == 0) s_enc[k_u][slot] = (int)(((s.encm >> lane) & kick_enc_bits<NP>()) != 0);
-    __syncthreads();
-    if (wv == 0) {
-        if (cmb) {
-            int er = 0;
-            for (int q = 0; q < nl; q++) er |= s_enc[q][lane];
-            gu64* es = (gu64*)(P.esum + ((size_t)(rf - 1) * 2 + dd) * 3 * P.lvx_stride + w0 + lane);
-            auto bits = [](double v) { return (unsigned long long)__double_as_longlong(v); };
-            __hip_atomic_store(es, bits(c2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(es + P.lvx_stride, bits(e2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(es + 2 * (size_t)P.lvx_stride, bits((double)er), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) __hip_atomic_store(item, (gen << 8) | 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    gu64* rvo = (gu64*)(P.rve + ((size_t)(rf - 1) * 2 + dd) * plane + w0 + (mine ? lane : 0));
+    gu64* es = (gu64*)(P.esum + ((size_t)(rf - 1) * 2 + dd) * 3 * P.lvx_stride + w0 + (mine ? lane : 0));
+    // (not cancellable inside a segment: cancels are seen at the epochs -- the segment-level cancel of team
+    // B's passes, segment_gated_c, measured slower here: config 4 0.645 -> 0.66 ms median step,
+    // profiles/r05r_config4_ab_cancel.jsonl)
+    (void)side_pass<NP, D3, false>(P, dd ? P.bwd : P.fwd, s, rf, mine, rvo, es, (size_t)P.lvx_stride, item, gen, nullptr,
+                                   ctag, s_sp, cancelled_now);
 }
 
 template <int NPV, bool D3V>
@@ -1552,18 +1576,13 @@ __global__ __launch_bounds__(256) void hedge_kernel(const DevPlan P, const int W
     const int lane = threadIdx.x & 63;
     const int slot = lane / L;
     const int pl_idx = lane % L;
-    const int nl = P.n_levels;
     const int g = blockIdx.x >> 1, dd = blockIdx.x & 1;
-    const DirSched& SR = dd ? P.bwd : P.fwd;
-    const int Er = SR.n_epochs;
     extern __shared__ unsigned long long s_key[];  // [W] the slots' keys (the score's bits; all ones: not ranked)
-    __shared__ double s_rv[2][RVM_MAX_LEVELS][64];
-    __shared__ int s_enc[RVM_MAX_LEVELS][64];
+    __shared__ SidePassLds s_sp;
     __shared__ int s_cnt[2][256];
     __shared__ unsigned long long s_ck[RVM_HEDGE_CAND];  // the candidates' keys and slots, in slot order
     __shared__ int s_ci[RVM_HEDGE_CAND];
     __shared__ int s_sel[64];  // this group's slots by rank
-    __shared__ int s_cancel[2];
     __shared__ unsigned long long s_gen, s_pref;
     __shared__ int s_need;
 #ifdef RVM_PROFILE
@@ -1585,7 +1604,7 @@ __global__ __launch_bounds__(256) void hedge_kernel(const DevPlan P, const int W
     };
     if (tid == 0) {
         s_marked = 0;
-        s_cancel[0] = stopped();
+        s_sp.cancel[0] = stopped();
     }
     __syncthreads();
     // (a block that stops on its mark is counted: hw[RVM_HW_STATS + 4], rvm_plan_hedge_marks; and a block
@@ -1597,7 +1616,7 @@ __global__ __launch_bounds__(256) void hedge_kernel(const DevPlan P, const int W
             __hip_atomic_store(hw + 2 + 2 * g + dd, (gen << 8) | 3ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     };
-    if (s_cancel[0]) {  // (before the slots are read)
+    if (s_sp.cancel[0]) {  // (before the slots are read)
         count_marked();
         return;
     }
@@ -1801,104 +1820,45 @@ __global__ __launch_bounds__(256) void hedge_kernel(const DevPlan P, const int W
     int status = RVM_STATUS_OK;
     double e2w;
     walker_setup<NP, D3, L>(rowv, pl_idx, hill_factor, s, status, e2w);
-    int k = wv < nl ? wv : -1;
-    k = __builtin_amdgcn_readfirstlane(k);
-    const int k_u = k < 0 ? 0 : k;
-    const bool work = k >= 0;
-    KickPrep<NP> kq0{};
-    if (work && Er > 0) kq0 = kick_prep<NP, L, D3>(s, 1.875);
-    constexpr int rf = 2;
-    const int m_r = P.mult[k_u] << rf;
-    const int nt_r = P.nt[k_u];
-    const bool late = P.late_mult > 0 && m_r >= P.late_mult;  // (the late vote: the same bits)
-    const double sc = ldexp(P.inv_mult[k_u], -rf);
-    const bool cmb = work && k == 0 && lane < cnt;
-    const int hx = g * WPB + (cmb ? lane : 0);
+    const bool mine = lane < cnt;
+    const int hx = g * WPB + (mine ? lane : 0);
     gu64* rvo = (gu64*)(P.hrv + (size_t)dd * P.lvx_emax * RVM_HEDGE_STRIDE + hx);
-    double c2 = 0.0, e2 = 0.0;
-    bool cancelled = false;
+    gu64* es = (gu64*)(P.hsum + (size_t)dd * 3 * RVM_HEDGE_STRIDE + hx);
+    gu64* done = hw + 2 + 2 * g + dd;
 #ifdef RVM_PROFILE
     const unsigned long long prt_loop0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    for (int e = 0; e < Er; e++) {
-        const int ns = __builtin_amdgcn_readfirstlane(work ? SR.seg_n[e] * m_r : 0);
-        // (a cancel lands within 64 steps: a wave it stops part-way holds a partial state, which the
-        // block discards -- the word stays set, and wave 0 reads it again before anything is published)
-        if (ns > 0)
-            (void)segment_gated_c<D3, NP, L, RVM_REFINE_GUESS>(s, kq0, SR.seg_h1[e] * sc, ns, nt_r, hw, nullptr, ctag, late);
-        if (work) {
-            const double v0 = star_vx<NP, L>(s);
-            if (pl_idx == 0) s_rv[e & 1][k_u][slot] = v0;
-        }
-        if (wv == 0 && lane == 0) s_cancel[e & 1] = stopped();
-        __syncthreads();
-        if (s_cancel[e & 1]) {
-            cancelled = true;
-            break;
-        }
-        if (cmb) {  // (the refinement kernel's combiner, expression for expression)
-            double rvx = 0.0, rv3 = 0.0;
-            for (int q = 0; q < nl; q++) rvx += P.lw[q] * s_rv[e & 1][q][lane];
-            for (int q = 1; q < nl; q++) rv3 += P.lw3[q] * s_rv[e & 1][q][lane];
-            const double ob = SR.obs_rv[e], s2 = SR.obs_s2[e];
-            const double r = rvx - ob;
-            c2 += (r * r) / s2;
-            e2 += fabs((rvx - rv3) * (r + (rv3 - ob))) / s2;
-            __hip_atomic_store(rvo + (size_t)e * RVM_HEDGE_STRIDE, (unsigned long long)__double_as_longlong(rvx),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    // (cancellable inside a segment: a cancel lands within 64 steps.  A wave it stops part-way holds a partial
+    // state, which the block discards -- the word stays set, and wave 0 reads it again before anything is
+    // published)
+    const int ended = side_pass<NP, D3, true>(P, dd ? P.bwd : P.fwd, s, 2, mine, rvo, es, (size_t)RVM_HEDGE_STRIDE, done,
+                                              gen, hw, ctag, s_sp, stopped);
 #ifdef RVM_PROFILE
     if (lane == 0 && RVM_RPROF_MAX_WAVES / 2 + (size_t)blockIdx.x * 8 + wv < RVM_RPROF_MAX_WAVES) {
-        // (timing build: the hedge blocks' records after the refinement kernel's, [9] bit 29 set)
+        // (timing build: the hedge blocks' records after the refinement kernel's, [9] bit 29 set; taken when
+        // the pass has returned, wave 0's after its stores)
         unsigned long long* o = rvm_rprof + (RVM_RPROF_MAX_WAVES / 2 + (size_t)blockIdx.x * 8 + wv) * RVM_RPROF_SLOTS;
         o[0] = prt_entry;
         o[1] = prt_loop0;
         o[2] = __builtin_amdgcn_s_memrealtime();
         o[3] = o[2];
-        o[9] = (unsigned long long)blockIdx.x | (1ull << 29) | ((unsigned long long)(cancelled ? 1 : 0) << 30);
-        o[10] = cancelled ? 0 : 1;
+        o[9] = (unsigned long long)blockIdx.x | (1ull << 29) | ((unsigned long long)(ended == 1 ? 1 : 0) << 30);
+        o[10] = ended == 1 ? 0 : 1;
         o[11] = (unsigned long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_REG_HW_ID
         o[4] = (unsigned long long)s_marked;
+        if (wv == 0 && ended == 0) o[5] = o[2];
     }
 #endif
-    if (cancelled) {
-        count_marked();
-        return;
-    }
-    if (work && pl_idx == 0) s_enc[k_u][slot] = (int)(((s.encm >> lane) & kick_enc_bits<NP>()) != 0);
-    __syncthreads();
-    if (wv == 0) {
-        // (a cancel that stopped another wave inside the last segment: seen here, after the barrier)
-        if (__builtin_amdgcn_readfirstlane((int)stopped())) {
-            count_marked();
-            return;
-        }
-        if (cmb) {
-            int er = 0;
-            for (int q = 0; q < nl; q++) er |= s_enc[q][lane];
-            gu64* es = (gu64*)(P.hsum + (size_t)dd * 3 * RVM_HEDGE_STRIDE + hx);
-            auto bits = [](double v) { return (unsigned long long)__double_as_longlong(v); };
-            __hip_atomic_store(es, bits(c2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(es + RVM_HEDGE_STRIDE, bits(e2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(es + 2 * RVM_HEDGE_STRIDE, bits((double)er), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0)
-            __hip_atomic_store(hw + 2 + 2 * g + dd, (gen << 8) | 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef RVM_PROFILE
-        if (lane == 0 && RVM_RPROF_MAX_WAVES / 2 + (size_t)blockIdx.x * 8 < RVM_RPROF_MAX_WAVES)
-            rvm_rprof[(RVM_RPROF_MAX_WAVES / 2 + (size_t)blockIdx.x * 8) * RVM_RPROF_SLOTS + 5] =
-                __builtin_amdgcn_s_memrealtime();
-#endif
-    }
+    if (ended) count_marked();
 }
 
-// the hedge kernel's dynamic LDS request on the current device: all the CU has left beside its static
-// LDS (no other block then shares its CU), with the attribute admitting it set once per device and
-// instantiation (prepare_refine_t, as refine_budget); 0: the kernel cannot run
-template <int NPV, bool D3V>
-static size_t hedge_budget() {
+// The dynamic LDS a kernel of this file may request on the current device: all the CU has left beside the
+// kernel's static LDS, with the attribute admitting it set once per device and kernel; 0 when that could
+// not be done.  rvm_plan_create calls it for the plan's kernels (prepare_refine), so a launch never changes
+// function attributes -- launches stay capturable -- and a plan whose schedule would not fit is refused
+// there, not at launch.
+template <auto Kernel>
+static size_t lds_budget() {
     static size_t budget[64] = {};
     static bool known[64] = {};
     int dev = 0;
@@ -1907,7 +1867,7 @@ static size_t hedge_budget() {
         return 0;
     }
     if (!known[dev]) {
-        const void* f = reinterpret_cast<const void*>(&hedge_kernel<NPV, D3V>);
+        const void* f = reinterpret_cast<const void*>(Kernel);
         hipFuncAttributes fa{};
         size_t b = 0;
         if (hipFuncGetAttributes(&fa, f) == hipSuccess && fa.sharedSizeBytes < (size_t)RVM_LDS_PER_CU) {
@@ -1919,6 +1879,17 @@ static size_t hedge_budget() {
         known[dev] = true;
     }
     return budget[dev];
+}
+// the hedge kernel's request: the whole remainder (no other block then shares its CU); 0: it cannot run
+template <int NPV, bool D3V>
+static size_t hedge_budget() {
+    return lds_budget<&hedge_kernel<NPV, D3V>>();
+}
+// the refinement kernel's budget for its staged schedule: the default 32 KB where no more could be had
+template <int NPV, bool D3V, int NW>
+static size_t refine_budget() {
+    const size_t b = lds_budget<&refine_kernel<NPV, D3V, NW>>();
+    return b ? b : 32 * 1024;
 }
 
 // groups of walker slots a hedge of this launch may take: two CUs each of those the likelihood grid
@@ -1949,32 +1920,6 @@ static hipError_t launch_hedge_t(const DevPlan& P, int W, double hill_factor, co
     return hipGetLastError();
 }
 
-// Dynamic-LDS budget of the refinement kernel on the current device (the CU's 160 KB less its static
-// LDS), with the attribute admitting it set once per device and instantiation.  rvm_plan_create
-// calls it (prepare_refine) so a launch never changes function attributes -- launches stay
-// capturable -- and a plan whose schedule would not fit is refused there, not at launch.
-template <int NPV, bool D3V, int NW>
-static size_t refine_budget() {
-    static size_t budget[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-        (void)hipGetLastError();
-        return 32 * 1024;
-    }
-    if (budget[dev] == 0) {
-        const void* f = reinterpret_cast<const void*>(&refine_kernel<NPV, D3V, NW>);
-        hipFuncAttributes fa{};
-        size_t b = 32 * 1024;
-        if (hipFuncGetAttributes(&fa, f) == hipSuccess && fa.sharedSizeBytes < (size_t)RVM_LDS_PER_CU) {
-            const size_t lim = (size_t)RVM_LDS_PER_CU - fa.sharedSizeBytes;
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lim) == hipSuccess) b = lim;
-        }
-        (void)hipGetLastError();
-        budget[dev] = b;
-    }
-    return budget[dev];
-}
-
 template <int NPV, bool D3V>
 static hipError_t launch_refine_t(const DevPlan& P, int W, const double* params, double hill_factor, double* logl,
                                   int32_t* status, double* rv_out, const StretchArgs& sa, int eager, int hedge,
@@ -1983,12 +1928,10 @@ static hipError_t launch_refine_t(const DevPlan& P, int W, const double* params,
     const int emax = P.fwd.n_epochs > P.bwd.n_epochs ? P.fwd.n_epochs : P.bwd.n_epochs;
     const size_t smem = (size_t)emax * 8 * sizeof(double);
     // (checked by rvm_plan_create: a launch that cannot run would leave the work lists' counts set)
-    // (refine_kernel NW: four waves per workgroup for up to four levels; RVM_REFINE_W4=0 forces eight, A/B)
-    static const bool w4_env = [] {
-        const char* e = getenv("RVM_REFINE_W4");
-        return !(e && e[0] == '0');
-    }();
-    const bool w4 = P.n_levels <= 4 && w4_env;
+    // (refine_kernel NW: four waves per workgroup for up to four levels; RVM_REFINE_W4=0 forces eight, A/B --
+    // read at every launch, so that one process can run both: tests/test_gpu_resolve.py)
+    const char* w4_env = getenv("RVM_REFINE_W4");
+    const bool w4 = P.n_levels <= 4 && !(w4_env && w4_env[0] == '0');
     if (smem > (w4 ? refine_budget<NPV, D3V, 4>() : refine_budget<NPV, D3V, 8>())) return hipErrorInvalidConfiguration;
     // every block reads the list sizes (the last one resets them): a grid of at most one block
     // per CU, and no more than the lists could fill
@@ -2022,7 +1965,7 @@ static hipError_t prepare_refine_t(const DevPlan& P) {
 }
 
 // the per-planet-count translation units (rvm_refine_np<N>.hip: one instantiation set each, so make -j
-// compiles them in parallel) export these
+// compiles them in parallel) export these; RVM_REFINE_NP_DEFINE(N) is the whole of such a file's code
 #define RVM_REFINE_NP_API(N)                                                                                     \
     hipError_t launch_refine_np##N(const DevPlan& P, int W, const double* params, double hill_factor, double* logl, \
                                    int32_t* status, double* rv_out, const StretchArgs& sa, int eager, int hedge, \
@@ -2038,5 +1981,30 @@ RVM_REFINE_NP_API(2)
 RVM_REFINE_NP_API(3)
 RVM_REFINE_NP_API(4)
 #undef RVM_REFINE_NP_API
+
+#define RVM_REFINE_NP_DEFINE(N)                                                                                     \
+    hipError_t rvm::launch_refine_np##N(const DevPlan& P, int W, const double* params, double hill_factor,         \
+                                        double* logl, int32_t* status, double* rv_out, const StretchArgs& sa,      \
+                                        int eager, int hedge, hipStream_t stream) {                                \
+        return P.inclined                                                                                           \
+                   ? launch_refine_t<N, true>(P, W, params, hill_factor, logl, status, rv_out, sa, eager, hedge, stream) \
+                   : launch_refine_t<N, false>(P, W, params, hill_factor, logl, status, rv_out, sa, eager, hedge, stream); \
+    }                                                                                                               \
+    hipError_t rvm::launch_eager_np##N(const DevPlan& P, int W, const double* params, double hill_factor,          \
+                                       hipStream_t stream) {                                                        \
+        return P.inclined ? launch_eager_t<N, true>(P, W, params, hill_factor, stream)                             \
+                          : launch_eager_t<N, false>(P, W, params, hill_factor, stream);                           \
+    }                                                                                                               \
+    int rvm::hedge_groups_np##N(const DevPlan& P, int W, int logl_blocks) {                                        \
+        return P.inclined ? hedge_groups_t<N, true>(P, W, logl_blocks) : hedge_groups_t<N, false>(P, W, logl_blocks); \
+    }                                                                                                               \
+    hipError_t rvm::launch_hedge_np##N(const DevPlan& P, int W, double hill_factor, const StretchArgs& sa, int ngrp, \
+                                       hipStream_t stream) {                                                        \
+        return P.inclined ? launch_hedge_t<N, true>(P, W, hill_factor, sa, ngrp, stream)                           \
+                          : launch_hedge_t<N, false>(P, W, hill_factor, sa, ngrp, stream);                         \
+    }                                                                                                               \
+    hipError_t rvm::prepare_refine_np##N(const DevPlan& P) {                                                       \
+        return P.inclined ? prepare_refine_t<N, true>(P) : prepare_refine_t<N, false>(P);                          \
+    }
 
 }  // namespace rvm

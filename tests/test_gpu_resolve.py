@@ -362,7 +362,8 @@ def test_t1_eccentricity_guard(W):
 def test_refinement_layouts_bit_identical(system):
     """The refinement kernel's layouts -- teams (passes 1, 2, 3 at once, the default; 2 and 4 teams),
     one team with each direction on its own workgroup (RVM_REFINE_TEAMS=0), both directions in one
-    workgroup (RVM_REFINE_SPLIT=0) -- take the same decisions with the same bits: speculative
+    workgroup (RVM_REFINE_SPLIT=0), and (s2) eight waves per workgroup instead of four
+    (RVM_REFINE_W4=0) -- take the same decisions with the same bits: speculative
     iterations of the sampler at a steady state (extensions, halving passes, certain rejects,
     two-pass walkers; HD155358's launches climb to passes 3 and 4), positions, log-probabilities and
     plan counters compared."""
@@ -383,8 +384,11 @@ def test_refinement_layouts_bit_identical(system):
         X0 = np.load(os.path.join(ROOT, "scripts", "probe", "ens_hd155358_it1000.npy"))
         iters = 6
     runs = []
-    for env in ({}, {"RVM_REFINE_TEAMS": "2"}, {"RVM_REFINE_TEAMS": "4"}, {"RVM_REFINE_TEAMS": "0"},
-                {"RVM_REFINE_SPLIT": "0"}):
+    envs = [{}, {"RVM_REFINE_TEAMS": "2"}, {"RVM_REFINE_TEAMS": "4"}, {"RVM_REFINE_TEAMS": "0"},
+            {"RVM_REFINE_SPLIT": "0"}]
+    if system == "s2":
+        envs.append({"RVM_REFINE_W4": "0"})  # (the eight-wave instantiation against the four-wave ones)
+    for env in envs:
         old = {k: os.environ.get(k) for k in env}
         os.environ.update(env)
         try:
