@@ -1,5 +1,6 @@
 // rvm_internal.h -- host/device shared launch descriptors of librvmcmc.so (not part of the ABI).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/rvmcmc.h"
@@ -100,6 +101,44 @@ struct DirSched {
     const double* obs_rv;     // observed RV
     const double* obs_s2;     // sigma^2
     const int32_t* obs_idx;   // index of the epoch in the plan's input order (rv_out rows)
+};
+
+// (always inlined on the device: a call pins the struct behind `this` to scratch)
+#ifdef __HIPCC__
+#define RVM_HD __host__ __device__ inline __attribute__((always_inline))
+#else
+#define RVM_HD inline
+#endif
+
+// The dynamic LDS of one logl_kernel block, in doubles from s_sched: the one statement of it for the kernel's
+// pointers, the launcher's request (choose_logl_layout) and the plan's worst case (prepare_logl).
+//   LDS-coupled  schedule 4 emax | staging (R + 3) G wpb when fused | t = 0 state G RVM_INIT_DOUBLES when
+//                rmax > 0 | ring [G][lc_ring][nl + 1][wpb]
+//   level-split  schedule 8 emax (both directions) | ring [2][NK][ring][wpb] | t = 0 state 2 RVM_INIT_DOUBLES
+struct LoglLds {
+    int split;        // 1: level-split
+    int emax, wpb;    // the longer direction's epochs; walkers per group
+    int units;        // walker groups (units) of a block
+    int stage_rows;   // LDS-coupled, fused: parameter rows + 3 (z, u, lnp), else 0
+    int init;         // 1: the lanes' t = 0 state is kept (rmax > 0)
+    int ring_epochs;  // epochs a ring holds per level
+    int ring_levels;  // levels per group (unit) in the ring
+    static RVM_HD LoglLds coupled(int emax, int wpb, int G, int rows, bool fused, bool init, int lc_ring, int nl) {
+        return LoglLds{0, emax, wpb, G, fused ? rows + 3 : 0, init ? 1 : 0, lc_ring, nl + 1};
+    }
+    static RVM_HD LoglLds level_split(int emax, int wpb, int nk, bool init) {  // (nk: levels per unit, 3; 4 with lsx)
+        return LoglLds{1, emax, wpb, 2, 0, init ? 1 : 0, emax < RVM_LS_RING ? emax : RVM_LS_RING, nk};
+    }
+    RVM_HD size_t sched_size() const { return (size_t)(split ? 8 : 4) * emax; }
+    RVM_HD size_t staging_size() const { return (size_t)stage_rows * units * wpb; }
+    RVM_HD size_t init_size() const { return init ? (size_t)units * RVM_INIT_DOUBLES : 0; }
+    RVM_HD size_t ring_size() const { return (size_t)units * ring_levels * ring_epochs * wpb; }
+    RVM_HD size_t sched_dir(int d) const { return split ? (size_t)d * 4 * emax : 0; }  // direction d's schedule
+    RVM_HD size_t staging() const { return sched_size(); }
+    RVM_HD size_t init_state() const { return sched_size() + (split ? ring_size() : staging_size()); }
+    RVM_HD size_t ring() const { return sched_size() + (split ? 0 : staging_size() + init_size()); }
+    RVM_HD size_t total() const { return sched_size() + staging_size() + init_size() + ring_size(); }
+    RVM_HD size_t bytes() const { return total() * sizeof(double); }
 };
 
 // Everything a logl launch needs, passed by value as the kernel argument.

@@ -7,6 +7,34 @@
 #include "rvm_internal.h"
 
 namespace rvm {
+// The dynamic LDS a kernel may request on the current device: all the CU has left beside the kernel's static
+// LDS, with the attribute admitting it set once per device and kernel; 0 when that could not be done.
+// rvm_plan_create calls it for the plan's kernels (prepare_logl, prepare_refine), so a launch never changes
+// function attributes -- launches stay capturable -- and a plan that would not fit is refused there.
+template <auto Kernel>
+static size_t lds_budget() {
+    static size_t budget[64] = {};
+    static bool known[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    if (!known[dev]) {
+        const void* f = reinterpret_cast<const void*>(Kernel);
+        hipFuncAttributes fa{};
+        size_t b = 0;
+        if (hipFuncGetAttributes(&fa, f) == hipSuccess && fa.sharedSizeBytes < (size_t)RVM_LDS_PER_CU) {
+            const size_t lim = (size_t)RVM_LDS_PER_CU - fa.sharedSizeBytes;
+            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lim) == hipSuccess) b = lim;
+        }
+        (void)hipGetLastError();
+        budget[dev] = b;
+        known[dev] = true;
+    }
+    return budget[dev];
+}
+
 hipError_t launch_logl(const DevPlan& P, int W, const double* params, double hill_factor, unsigned long long* slots,
                        double* logl, int32_t* status, double* rv_out, const StretchArgs& sa, hipStream_t stream,
                        int* dry_blocks);

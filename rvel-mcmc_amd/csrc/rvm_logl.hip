@@ -31,6 +31,7 @@
 #pragma clang fp contract(on)
 
 #include "rvm_launch.h"
+#include "rvm_plan_host.h"
 #include "rvm_walker.h"
 
 // the main pass's drifts with the fifth-order Kepler guess (rvm_device.h drift G5; A/B knob, off:
@@ -206,7 +207,8 @@ void logl_kernel(const DevPlan P, const int W,
     // encounter mask and speculation state, and the ready flag
     __shared__ double s_hos[2][8][64];
     __shared__ unsigned long long s_hoe[2];
-    __shared__ int s_hosp[2], s_hof[2];
+    __shared__ int s_hosp[2];  // (SpecState::pack)
+    __shared__ int s_hof[2];
     __shared__ int s_enc_all[2][RVM_MAX_LEVELS][64];
     // adaptive resolution: walker slots of each group (LDS-coupled) / unit (level-split) still above
     // the estimate bound; the level-split combiners' verdicts (0 pending, 1 finished, 2 refine) and
@@ -231,17 +233,20 @@ void logl_kernel(const DevPlan P, const int W,
     const double inv_mult = P.inv_mult[lvl_u];
     const int E = S.n_epochs;
     const int emax2 = P.fwd.n_epochs > P.bwd.n_epochs ? P.fwd.n_epochs : P.bwd.n_epochs;
-    double* l_dir = dec ? s_sched + (size_t)d * 4 * emax2 : s_sched;  // level-split: both directions staged
-    double* l_len = l_dir;
-    double* l_rv = l_dir + E;
-    double* l_s2 = l_dir + 2 * E;
-    int* l_n = reinterpret_cast<int*>(l_dir + 3 * E);
-    int* l_idx = l_n + E;
+    constexpr int PR = D3 ? 7 : 5;  // parameter rows per planet
+    constexpr int R = PR * NP;
+    const bool stretch = sa.c != nullptr;
+    const bool mh = sa.mh_scale != nullptr;  // fused MH step (rvm_mh_step)
+    const bool fused = stretch || mh;        // accepts at the end
+    // where everything in the dynamic LDS lies (LoglLds, rvm_internal.h: the launcher's request is its total)
+    const LoglLds lds = dec ? LoglLds::level_split(emax2, WPB, lsx ? 4 : 3, P.rmax > 0)
+                            : LoglLds::coupled(emax2, WPB, G, R, fused, P.rmax > 0, P.lc_ring, nl);
+    const SchedView sv(s_sched + lds.sched_dir(d), E);  // (level-split: both directions staged)
     // fused stretch half-step: the proposal rows, z, u3 and the current lnp of every walker of the
     // block, for the lane that finishes the walker (end of the kernel)
     const int GW = G * WPB;
     const int gi = grp * WPB + slot;  // walker slot within the block
-    double* l_q = s_sched + 4 * E;    // [rows][GW], then z | u3 | lnp0
+    double* l_q = s_sched + lds.staging();  // [rows][GW], then z | u3 | lnp0
     // first chunk of the schedule: loads issued now, stored to LDS after the setup below so their
     // latency hides behind the Pal conversion
     const int i0 = threadIdx.x;
@@ -258,10 +263,6 @@ void logl_kernel(const DevPlan P, const int W,
     // ---- walker parameters (m, a, h, k, l [, ix, iy] per planet), prior (state.py:299-315) -----
     // Fused stretch half-step (sa.c != nullptr): the walker's parameters are its proposal
     // q = c_j - z (c_j - x) mapped onto the kernel rows (rvm_stretch.h, rvm_param_map).
-    constexpr int PR = D3 ? 7 : 5;  // parameter rows per planet
-    const bool stretch = sa.c != nullptr;
-    const bool mh = sa.mh_scale != nullptr;  // fused MH step (rvm_mh_step)
-    const bool fused = stretch || mh;        // accepts at the end
     const bool mapped = fused || sa.fd_x != nullptr;  // parameters formed from StretchArgs
     double zst = 0.0, zp = 0.0;
     int jst = 0, jp = 0, kind = 0, wk = wl;
@@ -271,7 +272,6 @@ void logl_kernel(const DevPlan P, const int W,
     // sa.lnp holds just their n_spec (or W) entries -- half 1's slots must not read it
     const bool stager = !dec && fused && lvl == 0 && pl_idx == 0 && kind == 0;
     if (stager) {
-        constexpr int R = PR * NP;
         l_q[R * GW + gi] = zst;
         l_q[(R + 1) * GW + gi] = mh ? mh_u(sa.seed, (uint64_t)(sa.s0_begin + wl), sa.iteration)
                                     : stretch_u3(sa.seed, (uint64_t)(sa.s0_begin + wl), sa.iteration, sa.half);
@@ -280,7 +280,6 @@ void logl_kernel(const DevPlan P, const int W,
     // the walker's parameter rows; a fused MH step spreads its Box-Muller proposals over the
     // walker's planet lanes (lane q forms rows q, q + L, ...; DPP broadcast within the group), so
     // each lane draws ceil(R / L) normals instead of R -- same bits, a shorter prologue
-    constexpr int R = PR * NP;
     double rowv[R];
     if (L > 1 && mh) {
         constexpr int NI = (R + L - 1) / L;
@@ -323,20 +322,9 @@ void logl_kernel(const DevPlan P, const int W,
     // adaptive resolution: the lanes' state at t = 0 for refinement passes, in LDS after the
     // schedule and the stretch staging (LDS-coupled: [group][8][64]) or after the level-split ring
     // ([unit][8][64]; the unit's level-3 wave keeps it)
-    const int ring_sz = emax2 < RVM_LS_RING ? emax2 : RVM_LS_RING;
-    double* l_init = dec ? s_sched + (size_t)8 * emax2 + (size_t)2 * NK * ring_sz * WPB
-                         : s_sched + (size_t)4 * emax2 + (fused ? (size_t)(R + 3) * GW : 0);
-    if (P.rmax > 0 && (dec ? (bid < nA && wv < 2) : lvl == 0)) {
-        double* o = l_init + (size_t)(dec ? wv : grp) * RVM_INIT_DOUBLES + lane;
-        o[0] = s.rx;
-        o[64] = s.ry;
-        o[128] = s.vx;
-        o[192] = s.vy;
-        o[256] = s.rz;
-        o[320] = s.vz;
-        o[384] = s.r;
-        o[448] = s.ir;
-    }
+    double* l_init = s_sched + lds.init_state();
+    if (P.rmax > 0 && (dec ? (bid < nA && wv < 2) : lvl == 0))
+        lane_save(s, l_init + (size_t)(dec ? wv : grp) * RVM_INIT_DOUBLES + lane);
     // the interaction at t = 0 (the first segment's opening half kick) and REBOUND's check of
     // exit_min_distance before the first step -- when it integrates at all: get_rv of an empty
     // epoch list never does
@@ -348,35 +336,20 @@ void logl_kernel(const DevPlan P, const int W,
         if (threadIdx.x < 2 * (RVM_MAX_LEVELS + 1)) (&s_lcp[0][0])[threadIdx.x] = 0;
         if (threadIdx.x < 2) s_lcc[threadIdx.x] = 0;
         if (i0 < E) {
-            l_len[i0] = st_h;
-            l_rv[i0] = st_rv;
-            l_s2[i0] = st_s2;
-            l_n[i0] = st_n;
-            l_idx[i0] = st_idx;
+            sv.len[i0] = st_h;
+            sv.rv[i0] = st_rv;
+            sv.s2[i0] = st_s2;
+            sv.n[i0] = st_n;
+            sv.idx[i0] = st_idx;
         }
-        for (int i = i0 + blockDim.x; i < E; i += blockDim.x) {
-            l_len[i] = S.seg_h1[i];
-            l_rv[i] = S.obs_rv[i];
-            l_s2[i] = S.obs_s2[i];
-            l_n[i] = S.seg_n[i];
-            l_idx[i] = S.obs_idx[i];
-        }
+        stage_sched(S, sv, i0 + blockDim.x, blockDim.x);
     } else {
         if (threadIdx.x < 8) (&s_lvp[0][0])[threadIdx.x] = 0;
         if (threadIdx.x < 2) s_cprog[threadIdx.x] = 0;
         if (threadIdx.x < 2) s_hof[threadIdx.x] = 0;
         for (int dd = 0; dd < 2; dd++) {
             const DirSched& SD = dd ? P.bwd : P.fwd;
-            double* b = s_sched + (size_t)dd * 4 * emax2;
-            const int ED = SD.n_epochs;
-            int* bn = reinterpret_cast<int*>(b + 3 * ED);
-            for (int i = i0; i < ED; i += blockDim.x) {
-                b[i] = SD.seg_h1[i];
-                b[ED + i] = SD.obs_rv[i];
-                b[2 * ED + i] = SD.obs_s2[i];
-                bn[i] = SD.seg_n[i];
-                bn[ED + i] = SD.obs_idx[i];
-            }
+            stage_sched(SD, SchedView(s_sched + lds.sched_dir(dd), SD.n_epochs), i0, blockDim.x);
         }
     }
 
@@ -420,10 +393,38 @@ void logl_kernel(const DevPlan P, const int W,
 #ifdef RVM_PROFILE
     unsigned long long t_seg = 0, t_epo = 0;
 #endif
-    int redo = 0;      // speculative segments redone gated (counted in the timing build only)
-    int spec_off = 0;  // wave-uniform: segments left to run gated after a redo
-    int spec_bo = 4;   // wave-uniform: the next back-off, doubled by each redo (a walker whose orbit
-                       // keeps needing the general solver), back to 4 after a clean segment
+    int redo = 0;  // speculative segments redone gated (counted in the timing build only)
+    SpecState sp{0, 4};  // (wave-uniform)
+#ifdef RVM_PROFILE
+    // the wave's record (rvm_prof; scripts/probe/prof_kernel.py): f7 its level / direction / multiplier
+    // word; x the level-split waves' slots 11..13 -- end of integration, the combiner's arrival, the
+    // arrival word -- or null (left as they are)
+    auto prof_write = [&](const int gw, const unsigned long long f7, const unsigned long long* x) {
+        if (lane == 0 && gw < RVM_PROF_MAX_WAVES) {
+            unsigned long long* o = rvm_prof + (size_t)gw * RVM_PROF_SLOTS;
+            o[0] = t_start;
+            o[1] = t_pro;
+            o[2] = t_seg;
+            o[3] = t_epo;
+            o[4] = __builtin_readcyclecounter();
+            o[5] = rt_start;
+            o[6] = __builtin_amdgcn_s_memrealtime();
+            o[7] = f7;
+            o[8] = (unsigned long long)redo;
+            o[9] = (unsigned long long)E;
+            o[10] = (unsigned long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_REG_HW_ID
+            if (x != nullptr) {
+                o[11] = x[0];
+                o[12] = x[1];
+                o[13] = x[2];
+            }
+            o[14] = t_p1;
+            o[15] = t_p2;
+            o[16] = t_p3;
+            o[17] = t_p4;
+        }
+    };
+#endif
     double chi2 = 0.0;
     double est = 0.0;  // adaptive resolution: sum_e |(rv - o)^2 - (rv3 - o)^2| / s2 (combiner lanes)
     double c5x = 0.0, ddx = 0.0;  // the concurrent extension's chi2 and acceptance sum (cx)
@@ -431,8 +432,8 @@ void logl_kernel(const DevPlan P, const int W,
     // slot in the block's LDS ring ([unit ul][local level ks][RING][WPB] doubles after the schedule)
     const int ul = wv & 1;
     const int ks = lsx ? (lvl == 3 ? 0 : (lvl == 1 ? 1 : (lvl == 0 ? 2 : 3))) : (lvl == 3 ? 0 : (lvl == 2 ? 1 : 2));
-    const int RING = emax2 < RVM_LS_RING ? emax2 : RVM_LS_RING;
-    double* ring = s_sched + (size_t)8 * emax2;
+    const int RING = lds.ring_epochs;  // (the level-split ring: min(epochs, RVM_LS_RING))
+    double* ring = s_sched + lds.ring();
     gu64* lv1p = dec ? (gu64*)(P.lv_rv + ((size_t)d * P.lv_emax + e_lo) * P.lv_stride + wl) : nullptr;
     int rslot = RING > 0 ? e_lo % RING : 0;
     const int E_int = comb ? 0 : e_hi;  // the combiners integrate nothing
@@ -442,35 +443,22 @@ void logl_kernel(const DevPlan P, const int W,
         // a tail: wait for the head's state at epoch e_lo (same block, LDS); the head (type A: wave
         // + 2, type B: wave - 1) publishes its progress at every epoch
         const int head = bid < nA ? wv + 2 : wv - 1;
-        int seen = -1;
-        clk.restart();
-        while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&s_hof[hs], __ATOMIC_ACQUIRE,
-                                                                 __HIP_MEMORY_SCOPE_WORKGROUP)) == 0) {
-            const int pd = __builtin_amdgcn_readfirstlane(
-                __hip_atomic_load(s_done + head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-            if (pd != seen) {
-                seen = pd;
-                clk.restart();
-            } else if (clk.expired(P.spin_ticks)) {
-                wfault = true;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(8);
-        }
-        s.rx = s_hos[hs][0][lane];
-        s.ry = s_hos[hs][1][lane];
-        s.vx = s_hos[hs][2][lane];
-        s.vy = s_hos[hs][3][lane];
-        s.rz = s_hos[hs][4][lane];
-        s.vz = s_hos[hs][5][lane];
-        s.r = s_hos[hs][6][lane];
-        s.ir = s_hos[hs][7][lane];
+        wfault = wait_progress<8>(
+            clk, P.spin_ticks,
+            [&]() {
+                return __builtin_amdgcn_readfirstlane(
+                    __hip_atomic_load(s_done + head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+            },
+            [&](int) {
+                return __builtin_amdgcn_readfirstlane(
+                           __hip_atomic_load(&s_hof[hs], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) != 0;
+            });
+        lane_load(s, &s_hos[hs][0][lane]);
         // (readfirstlane is 32-bit signed: each half through `unsigned`, or a set bit 31 -- an
         // encounter on lane 30/31 -- would sign-extend into all 32 upper lanes)
         s.encm = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(s_hoe[hs] & 0xFFFFFFFFull)) |
                  ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(s_hoe[hs] >> 32)) << 32);
-        spec_off = __builtin_amdgcn_readfirstlane(s_hosp[hs]) & 0xFFFF;
-        spec_bo = __builtin_amdgcn_readfirstlane(s_hosp[hs]) >> 16;
+        sp = SpecState::unpack(__builtin_amdgcn_readfirstlane(s_hosp[hs]));
         // the interaction at the hand-off epoch, from the same positions: the head's bits (its
         // encounter test repeats on positions the head already tested)
         kp = kick_prep<NP, L, D3>(s, 1.875);
@@ -478,9 +466,7 @@ void logl_kernel(const DevPlan P, const int W,
     // (LDS-coupled) this group's ring of the levels' star vx, after the lanes' t = 0 state
     const int NLC = nl + (cx ? 1 : 0);  // levels that publish (the extension wave too)
     const int RC = P.lc_ring;  // (rvm_plan_create: min(RVM_LC_RING, epochs), within RVM_LC_RING_BYTES)
-    double* lring = dec ? nullptr
-                        : l_init + (P.rmax > 0 ? (size_t)G * RVM_INIT_DOUBLES : 0) +
-                              (size_t)grp * RC * (nl + 1) * WPB;
+    double* lring = dec ? nullptr : s_sched + lds.ring() + (size_t)grp * RC * (nl + 1) * WPB;
     // (LDS-coupled) the combiner's side: the epochs every other level has published (wave-uniform),
     // a bounded wait for epoch ec, and the combine of epoch ec -- Richardson RV, chi2, estimate, the
     // extension's sums, the RV for a refinement -- in epoch order (the bits of the barrier-coupled
@@ -493,6 +479,9 @@ void logl_kernel(const DevPlan P, const int W,
         return __builtin_amdgcn_readfirstlane(mn);
     };
     auto lc_wait = [&](const int ec) {
+        // wait_progress (rvm_walker.h) written out, here and at the levels' wait below: through the call the
+        // 3-planet paired layout ran slower than the parent; the
+        // level-split waits call it -- a change to one is a change to all
         int seen = -1;
         clk.restart();
         for (;;) {
@@ -511,23 +500,21 @@ void logl_kernel(const DevPlan P, const int W,
     auto lc_combine = [&](const int ec) {
         const double* rv_e = lring + (size_t)(ec % RC) * (nl + 1) * WPB;
         if (lane < WPB) {  // lane `lane` of level 0's wave owns walker slot `lane`
-            double rvx = 0.0, rv3 = 0.0;
-            for (int k = 0; k < nl; k++) rvx += P.lw[k] * rv_e[(size_t)k * WPB + lane];
-            for (int k = 1; k < nl; k++) rv3 += P.lw3[k] * rv_e[(size_t)k * WPB + lane];
-            const double r = rvx - l_rv[ec];
-            chi2 += (r * r) / l_s2[ec];
-            est += fabs((rvx - rv3) * (r + (rv3 - l_rv[ec]))) / l_s2[ec];
             const int wo = w0 + lane;
-            if (rv_out != nullptr && wo < W) rv_out[(size_t)l_idx[ec] * W + wo] = rvx;
-            if (P.ext_mult > 0 && wo < W) {  // the RV and the extension's partial sum, for a refinement
-                double s5 = 0.0;
-                for (int k = 0; k < nl; k++) s5 += P.lw5[k] * rv_e[(size_t)k * WPB + lane];
+            const bool keep = P.ext_mult > 0 && wo < W;  // the RV and the extension's partial sum, for a refinement
+            double rvx, rv3, dc2, de2, s5;
+            combine_epoch(P, nl, [&](int k) { return rv_e[(size_t)k * WPB + lane]; }, sv.rv[ec], sv.s2[ec], rvx, rv3,
+                          dc2, de2, keep, s5);
+            chi2 += dc2;
+            est += de2;
+            if (rv_out != nullptr && wo < W) rv_out[(size_t)sv.idx[ec] * W + wo] = rvx;
+            if (keep) {
                 const size_t xi = (size_t)(d * P.lvx_emax + ec) * P.lvx_stride + wo;
                 if (cx) {  // (extend_pass's sums, from the extension wave's value of this epoch)
-                    const double r5 = s5 + P.lw5[nl] * rv_e[(size_t)nl * WPB + lane];
-                    const double q = r5 - l_rv[ec];
-                    c5x += (q * q) / l_s2[ec];
-                    ddx += fabs((r5 - rvx) * (q + (rvx - l_rv[ec]))) / l_s2[ec];
+                    double r5, dc5, dd5;
+                    extension_epoch(s5, P.lw5[nl], rv_e[(size_t)nl * WPB + lane], rvx, sv.rv[ec], sv.s2[ec], r5, dc5, dd5);
+                    c5x += dc5;
+                    ddx += dd5;
                 } else {
                     P.lvx[xi] = s5;
                 }
@@ -537,12 +524,12 @@ void logl_kernel(const DevPlan P, const int W,
         // (the combiner has read epoch ec: its ring slot may be rewritten)
         if (lane == 0) __hip_atomic_store(&s_lcc[grp], ec + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
-    int n1 = e_lo < E ? l_n[e_lo] : 0;
-    double len = e_lo < E ? l_len[e_lo] : 0.0;
+    int n1 = e_lo < E ? sv.n[e_lo] : 0;
+    double len = e_lo < E ? sv.len[e_lo] : 0.0;
     for (int e = e_lo; e < E_int; e++) {
         // prefetch the next segment while this one integrates
-        const int n1_next = e + 1 < E ? l_n[e + 1] : 0;
-        const double len_next = e + 1 < E ? l_len[e + 1] : 0.0;
+        const int n1_next = e + 1 < E ? sv.n[e + 1] : 0;
+        const double len_next = e + 1 < E ? sv.len[e + 1] : 0.0;
         const int ns = n1 * mult;
         // the partner's remaining work, read now and used after the segment (latency hidden)
         int rem_oth = 0, done_oth = 0;
@@ -553,20 +540,19 @@ void logl_kernel(const DevPlan P, const int W,
         PROF_T(ta);
         if (ns > 0) {
             const double h = len * inv_mult;  // len holds the segment's base step
-            if (spec) {  // (implies nt == 6)
-                // speculate unless a recent segment of this wave needed a redo: walkers whose
-                // orbits keep needing the general solver (short periods, high eccentricity in a
-                // wide ensemble) then run gated for a while instead of paying for redos
-                if (spec_off == 0) {
+            // segment_backoff (rvm_walker.h) written out: through the call the 3-planet LDS-coupled kernel no
+            // longer fits its 168 VGPRs; a change to one is a change to both
+            if (spec) {  // (implies nt <= 6)
+                if (sp.off == 0) {
                     if (segment<6, true, D3, NP, L, RVM_MAIN_G5 != 0>(s, kp, h, ns, redo)) {
-                        spec_off = spec_bo;
-                        spec_bo = spec_bo < 64 ? 2 * spec_bo : 64;
+                        sp.off = sp.bo;
+                        sp.bo = sp.bo < 64 ? 2 * sp.bo : 64;
                     } else {
-                        spec_bo = 4;
+                        sp.bo = 4;
                     }
                 } else {
                     segment<6, false, D3, NP, L, RVM_MAIN_G5 != 0>(s, kp, h, ns, redo);
-                    spec_off--;
+                    sp.off--;
                 }
             } else if (nt <= 6)
                 segment<6, false, D3, NP, L, RVM_MAIN_G5 != 0>(s, kp, h, ns, redo);
@@ -602,22 +588,14 @@ void logl_kernel(const DevPlan P, const int W,
                 lv1p += P.lv_stride;
             } else {
                 // wait while the combiner is a whole ring behind (only when E > RING)
-                if (E > RING && !wfault) {
-                    int seen = -1;
-                    for (;;) {
-                        const int cp = __builtin_amdgcn_readfirstlane(
-                            __hip_atomic_load(s_cprog + ul, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
-                        if (e - cp < RING) break;
-                        if (cp != seen) {
-                            seen = cp;
-                            clk.restart();
-                        } else if (clk.expired(P.spin_ticks)) {
-                            wfault = true;
-                            break;
-                        }
-                        __builtin_amdgcn_s_sleep(4);
-                    }
-                }
+                if (E > RING && !wfault)
+                    wfault = wait_progress<4>(
+                        clk, P.spin_ticks,
+                        [&]() {
+                            return __builtin_amdgcn_readfirstlane(
+                                __hip_atomic_load(s_cprog + ul, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
+                        },
+                        [&](int cp) { return e - cp < RING; });
                 if (pl_idx == 0) ring[((ul * NK + ks) * RING + rslot) * WPB + slot] = v0;
                 if (lane == 0) __hip_atomic_store(&s_lvp[ul][ks], e + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 rslot = rslot + 1 == RING ? 0 : rslot + 1;
@@ -641,7 +619,7 @@ void logl_kernel(const DevPlan P, const int W,
                     if (!wfault) lc_combine(next_c++);
                 }
             } else if (E > RC && !wfault && e >= RC) {
-                int seen = -1;
+                int seen = -1;  // (wait_progress written out, as lc_wait)
                 for (;;) {
                     const int cp = __builtin_amdgcn_readfirstlane(
                         __hip_atomic_load(&s_lcc[grp], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
@@ -786,24 +764,9 @@ void logl_kernel(const DevPlan P, const int W,
                            double& c5o, double& ddo) __attribute__((always_inline)) {
         const DirSched& SR = dr ? P.bwd : P.fwd;
         const int Er = SR.n_epochs;
-        const double* r_dir = dec ? s_sched + (size_t)dr * 4 * emax2 : l_dir;
-        const double* r_len = r_dir;
-        const double* r_rv = r_dir + Er;
-        const double* r_s2 = r_dir + 2 * Er;
-        const int* r_n = reinterpret_cast<const int*>(r_dir + 3 * Er);
-        const int* r_idx = r_n + Er;
-        {
-            const double* in = l_init + (size_t)gr * RVM_INIT_DOUBLES + lane;
-            s.rx = in[0];
-            s.ry = in[64];
-            s.vx = in[128];
-            s.vy = in[192];
-            s.rz = in[256];
-            s.vz = in[320];
-            s.r = in[384];
-            s.ir = in[448];
-            s.encm = 0;
-        }
+        const SchedView rs(s_sched + lds.sched_dir(dr), Er);
+        lane_load(s, l_init + (size_t)gr * RVM_INIT_DOUBLES + lane);
+        s.encm = 0;
         KickPrep<NP> kq{};
         if (Er > 0) kq = kick_prep<NP, L, D3>(s, 1.875);
         const int mx = P.ext_mult;
@@ -817,42 +780,23 @@ void logl_kernel(const DevPlan P, const int W,
         const double* xr = P.rvp + xb;
         double a5 = cl && Er > 0 ? xs[0] : 0.0, a4 = cl && Er > 0 ? xr[0] : 0.0;
         double c5 = 0.0, dd = 0.0;
-        int x_off = 0, x_bo = 4;  // speculation back-off (as the main pass's spec_off / spec_bo)
+        SpecState xsp{0, 4};  // (the main pass's speculation policy: same bits)
         for (int e = 0; e < Er; e++) {
             const bool nx = cl && e + 1 < Er;
             const double b5 = nx ? xs[(size_t)(e + 1) * P.lvx_stride] : 0.0;
             const double b4 = nx ? xr[(size_t)(e + 1) * P.lvx_stride] : 0.0;
-            const int ns = r_n[e] * mx;
-            if (ns > 0) {
-                const double h = r_len[e] * ix;
-                if (P.ext_spec && ntx <= 6) {  // (the main pass's speculation policy: same bits)
-                    if (x_off == 0) {
-                        if (segment<6, true, D3, NP, L, RVM_MAIN_G5 != 0>(s, kq, h, ns, dummy_redo)) {
-                            x_off = x_bo;
-                            x_bo = x_bo < 64 ? 2 * x_bo : 64;
-                        } else {
-                            x_bo = 4;
-                        }
-                    } else {
-                        segment<6, false, D3, NP, L, RVM_MAIN_G5 != 0>(s, kq, h, ns, dummy_redo);
-                        x_off--;
-                    }
-                } else if (ntx <= 6)
-                    segment<6, false, D3, NP, L, RVM_MAIN_G5 != 0>(s, kq, h, ns, dummy_redo);
-                else if (ntx == 7)
-                    segment<7, false, D3, NP, L, RVM_MAIN_G5 != 0>(s, kq, h, ns, dummy_redo);
-                else
-                    segment<8, false, D3, NP, L, RVM_MAIN_G5 != 0>(s, kq, h, ns, dummy_redo);
-            }
+            const int ns = rs.n[e] * mx;
+            if (ns > 0)
+                segment_backoff<D3, NP, L, RVM_MAIN_G5 != 0>(s, kq, rs.len[e] * ix, ns, ntx, P.ext_spec && ntx <= 6, xsp,
+                                                             dummy_redo);
             const double v = star_vx<NP, L>(s);
             const double vx = __shfl(v, cs * L);
             if (cl) {
-                const double r = a4;
-                const double r5 = a5 + P.lw5[nl] * vx;
-                const double q = r5 - r_rv[e];
-                c5 += (q * q) / r_s2[e];
-                dd += fabs((r5 - r) * (q + (r - r_rv[e]))) / r_s2[e];
-                if (rv_out != nullptr && wo < W) rv_out[(size_t)r_idx[e] * W + wo] = r5;
+                double r5, dc5, dd5;
+                extension_epoch(a5, P.lw5[nl], vx, a4, rs.rv[e], rs.s2[e], r5, dc5, dd5);
+                c5 += dc5;
+                dd += dd5;
+                if (rv_out != nullptr && wo < W) rv_out[(size_t)rs.idx[e] * W + wo] = r5;
             }
             a5 = b5;
             a4 = b4;
@@ -862,15 +806,12 @@ void logl_kernel(const DevPlan P, const int W,
             c5o = c5;
             ddo = dd;
         }
-        if (cl && need) {
-            if (xenc) {
-                enc |= 1;
-                chi2w = c5;
-                need = false;
-            } else if (dd <= RVM_EXT_ACCEPT * P.rtol_dir * P.npoints) {  // (false for a non-finite one)
-                chi2w = c5;
-                need = false;
-            }
+        // (no test of a coarse-only encounter here, unlike the concurrent extensions': extension_verdict)
+        const int xv = cl && need ? extension_verdict(P, xenc, dd, false) : 0;
+        if (xv) {
+            enc |= xv >> 1;
+            chi2w = c5;
+            need = false;
         }
     };
     // The extension stage over the walker slots marked in s_need[g] of the active groups (gmask;
@@ -892,17 +833,6 @@ void logl_kernel(const DevPlan P, const int W,
             __syncthreads();
         }
     };
-    // a combiner lane's direction after the main pass and the extension: open (need) with the lower
-    // bound on its chi2 (oracle/rvoracle.c dir_extend: the extension's when it is finite, else the
-    // main pass's with its estimate alone), or settled; without halving passes (rmax = 0) an open
-    // direction is UNRESOLVED
-    auto direction_lb = [&](const bool need, const double chi2_main, const double est_raw, const bool xran,
-                            const double xc5, const double xdd) __attribute__((always_inline)) {
-        if (!need) return 0.0;
-        if (xran && isfinite(xc5) && isfinite(xdd)) return open_lb(xc5, xdd, est_raw);
-        return open_lb(chi2_main, INFINITY, est_raw);
-    };
-
     if (!dec) {
         if (pl_idx == 0) s_enc[lvl][slot] = encflag;
         __syncthreads();
@@ -913,31 +843,20 @@ void logl_kernel(const DevPlan P, const int W,
         // of ending the walker, DevPlan::fin_level; `cenc`)
         bool cenc = false;
         if (cmb) {
-            int encc = 0;
-            for (int k = 0; k < nl; k++) {
-                const int f = s_enc[k][lane];
-                if (k == P.fin_level || !(P.rtol_dir < INFINITY)) {
-                    enc |= f;
-                } else {
-                    enc |= f & ~1;
-                    encc |= f & 1;
-                }
-            }
-            cenc = encc != 0 && (enc & 1) == 0;
+            int encs = 0;
+            for (int k = 0; k < nl; k++) encs |= level_flags(s_enc[k][lane], k == P.fin_level, P.rtol_dir < INFINITY);
+            cenc = coarse_only_encounter(encs);
+            enc = encs & ~RVM_ENC_COARSE;
         }
         double chi2w = chi2;
         bool need = false;
         double lbw = 0.0;
         if (P.rtol_dir < INFINITY) {  // (kernel argument: uniform)
-            // (a non-finite chi2 -- the fixed step blowing up on an extreme orbit -- refines too, and
-            // so does a walker past the eccentricity guard: its e^2 from the walker's first lane,
-            // and one whose coarser levels alone came within the exit distance -- its main pass,
-            // like a non-finite one, neither settles nor bounds it: the stored RV of a refinement's
-            // first step-doubling change is invalidated, oracle/rvoracle.c dir_main `bad`)
+            // (direction_open; the walker's e^2 from its first lane.  A direction whose coarser levels
+            // alone came within the exit distance: its main pass, like a non-finite one, neither settles
+            // nor bounds it -- the stored RV of a refinement's first step-doubling change is invalidated)
             const double e2c = __shfl(e2w, (lane & (WPB - 1)) * L);
-            need = cmb && wo < W && enc == 0 &&
-                   (est / P.npoints > P.rtol_dir || !isfinite(chi2w) || !isfinite(est) ||
-                    (P.ext_mult > 0 && e2c > P.e2_guard) || cenc);
+            need = cmb && wo < W && direction_open(P, enc, chi2w, est, e2c, cenc);
             if (cenc && need && P.ext_mult > 0)
                 for (int e = 0; e < E; e++) P.rvp[(size_t)(d * P.lvx_emax + e) * P.lvx_stride + wo] = __builtin_nan("");
             if (P.rmax == 0) {
@@ -952,15 +871,11 @@ void logl_kernel(const DevPlan P, const int W,
                         if (lane == 0 && nx)
                             __hip_atomic_fetch_add(P.counters + 3, (unsigned long long)__builtin_popcountll(nx),
                                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (need) {
-                            if (s_enc[nl][lane] & 1) {
-                                enc |= 1;
-                                chi2w = c5x;
-                                need = false;
-                            } else if (!cenc && ddx <= RVM_EXT_ACCEPT * P.rtol_dir * P.npoints) {
-                                chi2w = c5x;
-                                need = false;
-                            }
+                        const int xv = need ? extension_verdict(P, (s_enc[nl][lane] & 1) != 0, ddx, cenc) : 0;
+                        if (xv) {
+                            enc |= xv >> 1;
+                            chi2w = c5x;
+                            need = false;
                         }
                     }
                 } else if (P.ext_mult > 0) {
@@ -972,9 +887,7 @@ void logl_kernel(const DevPlan P, const int W,
                     if ((s_need[0] | (G > 1 ? s_need[1] : 0ull)) != 0)
                         extend_stage(lvl, grp, d, need, chi2w, enc, c5x, ddx);
                 }
-                // (the extension's bound only below the cut guard, DevPlan::e2_cut)
-                lbw = cenc ? 0.0 : direction_lb(need, chi2, est, need0 && P.ext_mult > 0 && (e2c <= P.e2_cut || P.cut_guard_k > 0.0), c5x,
-                                                   e2c <= P.e2_cut ? ddx : P.cut_guard_k * ddx);
+                lbw = guarded_lb(P, need, chi2, est, need0 && P.ext_mult > 0, e2c > P.e2_cut, cenc, c5x, ddx);
             }
         }
         if (cmb && wo < W) {
@@ -992,46 +905,20 @@ void logl_kernel(const DevPlan P, const int W,
 #ifdef RVM_PROFILE
         const unsigned long long rt_integ = __builtin_amdgcn_s_memrealtime();
         auto prof_dec = [&](unsigned long long rt_arr, int arr) {
-            const int gw = (int)blockIdx.x * (blockDim.x >> 6) + wv;
-            if (lane == 0 && gw < RVM_PROF_MAX_WAVES) {
-                unsigned long long* o = rvm_prof + (size_t)gw * RVM_PROF_SLOTS;
-                o[0] = t_start;
-                o[1] = t_pro;
-                o[2] = t_seg;
-                o[3] = t_epo;
-                o[4] = __builtin_readcyclecounter();
-                o[5] = rt_start;
-                o[6] = __builtin_amdgcn_s_memrealtime();
-                // (level field 7: a combiner)
-                o[7] = (unsigned long long)(comb || (part == 1 && bid < nA) ? 7 : lvl) | ((unsigned long long)d << 8) |
-                       ((unsigned long long)mult << 16) |
-                       ((unsigned long long)part << 24);
-                o[8] = (unsigned long long)redo;
-                o[9] = (unsigned long long)E;
-                o[10] = (unsigned long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);
-                o[11] = rt_integ;
-                o[12] = rt_arr;
-                o[13] = (unsigned long long)arr | ((unsigned long long)unit_of() << 8);
-                o[14] = t_p1;
-                o[15] = t_p2;
-                o[16] = t_p3;
-                o[17] = t_p4;
-            }
+            // (level field 7: a combiner)
+            const unsigned long long x[3] = {rt_integ, rt_arr, (unsigned long long)arr | ((unsigned long long)unit_of() << 8)};
+            prof_write((int)blockIdx.x * (blockDim.x >> 6) + wv,
+                       (unsigned long long)(comb || (part == 1 && bid < nA) ? 7 : lvl) | ((unsigned long long)d << 8) |
+                           ((unsigned long long)mult << 16) | ((unsigned long long)part << 24),
+                       x);
         };
 #endif
         if (part == 1) {
             // a head: hand the state over to the tail and leave
-            s_hos[hs][0][lane] = s.rx;
-            s_hos[hs][1][lane] = s.ry;
-            s_hos[hs][2][lane] = s.vx;
-            s_hos[hs][3][lane] = s.vy;
-            s_hos[hs][4][lane] = s.rz;
-            s_hos[hs][5][lane] = s.vz;
-            s_hos[hs][6][lane] = s.r;
-            s_hos[hs][7][lane] = s.ir;
+            lane_save(s, &s_hos[hs][0][lane]);
             if (lane == 0) {
                 s_hoe[hs] = s.encm;
-                s_hosp[hs] = spec_off | (spec_bo << 16);
+                s_hosp[hs] = sp.pack();
                 __hip_atomic_store(&s_hof[hs], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
             if (bid >= nA) {  // (type-B heads have no combiner role)
@@ -1102,25 +989,19 @@ void logl_kernel(const DevPlan P, const int W,
                     v[2] = rg[(ul * 3 + 1) * rs];
                     v[3] = rg[(ul * 3 + 0) * rs];
                 }
-                double rvx = 0.0, rv3 = 0.0;
-#pragma unroll
-                for (int k = 0; k < 4; k++) rvx += P.lw[k] * v[k];
-#pragma unroll
-                for (int k = 1; k < 4; k++) rv3 += P.lw3[k] * v[k];
-                const double r = rvx - l_rv[e];
-                chi2w += (r * r) / l_s2[e];
-                est += fabs((rvx - rv3) * (r + (rv3 - l_rv[e]))) / l_s2[e];
-                if (rv_out != nullptr && valid && pl_idx == 0) rv_out[(size_t)l_idx[e] * W + w] = rvx;
-                if (P.ext_mult > 0 && valid && pl_idx == 0) {  // the RV and the extension's partial sum
-                    double s5 = 0.0;
-#pragma unroll
-                    for (int k = 0; k < 4; k++) s5 += P.lw5[k] * v[k];
+                const bool keep = P.ext_mult > 0 && valid && pl_idx == 0;  // the RV and the extension's partial sum
+                double rvx, rv3, dc2, de2, s5;
+                combine_epoch(P, 4, [&](int k) { return v[k]; }, sv.rv[e], sv.s2[e], rvx, rv3, dc2, de2, keep, s5);
+                chi2w += dc2;
+                est += de2;
+                if (rv_out != nullptr && valid && pl_idx == 0) rv_out[(size_t)sv.idx[e] * W + w] = rvx;
+                if (keep) {
                     const size_t xi = (size_t)(d * P.lvx_emax + e) * P.lvx_stride + w;
                     if (lsx) {  // (extend_pass's sums, from the extension wave's value of this epoch)
-                        const double r5 = s5 + P.lw5[nl] * rg[(ul * 4 + 3) * rs];
-                        const double q = r5 - l_rv[e];
-                        c5x += (q * q) / l_s2[e];
-                        ddx += fabs((r5 - rvx) * (q + (rvx - l_rv[e]))) / l_s2[e];
+                        double r5, dc5, dd5;
+                        extension_epoch(s5, P.lw5[nl], rg[(ul * 4 + 3) * rs], rvx, sv.rv[e], sv.s2[e], r5, dc5, dd5);
+                        c5x += dc5;
+                        ddx += dd5;
                         // the RV for a refinement's first step-doubling change, kept in level 0's ring
                         // slot (read; the ring holds the whole direction) and written to HBM only for
                         // the walkers the refinement kernel gets (below)
@@ -1196,12 +1077,9 @@ void logl_kernel(const DevPlan P, const int W,
                 hung = clk.expired(P.spin_ticks);
             }
             // (slot 0 is level 3, the finest; lsx: [3] the extension; the HBM-handed level's in f1)
-            int enc = s_encl[ul][0][slot] | s_encl[ul][1][slot] | s_encl[ul][2][slot];
-            int encc = 0;  // (adaptive: the coarser levels' encounter bits, DevPlan::fin_level)
-            if (P.rtol_dir < INFINITY) {
-                encc = (s_encl[ul][1][slot] | s_encl[ul][2][slot]) & 1;
-                enc = s_encl[ul][0][slot] | ((s_encl[ul][1][slot] | s_encl[ul][2][slot]) & ~1);
-            }
+            const bool adaptive = P.rtol_dir < INFINITY;
+            int encs = 0;  // (adaptive: the coarser levels' encounter bits apart, DevPlan::fin_level)
+            for (int k = 0; k < 3; k++) encs |= level_flags(s_encl[ul][k][slot], k == 0, adaptive);
             {
                 f1 = valid ? f1 : 0;
                 if (ballot(f1 < 0) != 0 && !hung) {
@@ -1212,15 +1090,10 @@ void logl_kernel(const DevPlan P, const int W,
                     } while (ballot(f1 < 0) != 0 && !hung);
                 }
                 if (valid && pl_idx == 0) __hip_atomic_store(e1p, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const int f1p = f1 > 0 ? f1 : 0;
-                if (P.rtol_dir < INFINITY) {
-                    enc |= f1p & ~1;
-                    encc |= f1p & 1;
-                } else {
-                    enc |= f1p;
-                }
+                encs |= level_flags(f1 > 0 ? f1 : 0, false, adaptive);
             }
-            const bool cenc = encc != 0 && (enc & 1) == 0;
+            const bool cenc = coarse_only_encounter(encs);
+            int enc = encs & ~RVM_ENC_COARSE;
             if (hung) {  // never completed (or a dirty workspace): NONFINITE, and the give-up counted
                 chi2w = __builtin_nan("");
                 enc |= RVM_ENC_FAULT;
@@ -1231,9 +1104,7 @@ void logl_kernel(const DevPlan P, const int W,
             const unsigned long long rt_arr = __builtin_amdgcn_s_memrealtime();
 #endif
             // adaptive resolution: settled, or open (with its lower bound) for the refinement kernel
-            bool need = P.rtol_dir < INFINITY && valid && pl_idx == 0 && enc == 0 &&
-                        (est / P.npoints > P.rtol_dir || !isfinite(chi2w) || !isfinite(est) ||
-                         (P.ext_mult > 0 && e2w > P.e2_guard) || cenc);
+            bool need = adaptive && valid && pl_idx == 0 && direction_open(P, enc, chi2w, est, e2w, cenc);
             // (a coarse-only encounter's main pass neither settles nor bounds the direction: its
             // stored RV for a refinement's first step-doubling change is invalidated)
             if (cenc && need && !lsx && P.ext_mult > 0)
@@ -1249,15 +1120,11 @@ void logl_kernel(const DevPlan P, const int W,
                 if (lane == 0 && nx)
                     __hip_atomic_fetch_add(P.counters + 3, (unsigned long long)__builtin_popcountll(nx),
                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (need) {
-                    if (s_encl[ul][3][slot] & 1) {
-                        enc |= 1;
-                        chi2w = c5x;
-                        need = false;
-                    } else if (!cenc && ddx <= RVM_EXT_ACCEPT * P.rtol_dir * P.npoints) {
-                        chi2w = c5x;
-                        need = false;
-                    }
+                const int xv = need ? extension_verdict(P, (s_encl[ul][3][slot] & 1) != 0, ddx, cenc) : 0;
+                if (xv) {
+                    enc |= xv >> 1;
+                    chi2w = c5x;
+                    need = false;
                 }
             }
             if (!lsx && P.ext_mult > 0 && ballot(need) != 0) {
@@ -1284,8 +1151,7 @@ void logl_kernel(const DevPlan P, const int W,
                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 double xc5 = 0.0, xdd = 0.0;
                 extend_pass(ul, d, nm, nd, c2, en, xc5, xdd);
-                const double lb = cn ? 0.0 : direction_lb(nd, cm, es, (f & 16) != 0 && ((f & 64) == 0 || P.cut_guard_k > 0.0), xc5,
-                                                                 (f & 64) != 0 ? P.cut_guard_k * xdd : xdd);
+                const double lb = guarded_lb(P, nd, cm, es, (f & 16) != 0, (f & 64) != 0, cn, xc5, xdd);
                 if (cl) finish_recompute(w0 + lane, c2, en, nd, lb);
             } else if (valid && pl_idx == 0) {
                 if (lsx && need) {  // the main pass's RV of an open direction (the ring, consume above)
@@ -1294,8 +1160,7 @@ void logl_kernel(const DevPlan P, const int W,
                         P.rvp[(size_t)(d * P.lvx_emax + e) * P.lvx_stride + w] = cenc ? __builtin_nan("") : rg[(size_t)e * WPB];
                 }
                 finish_recompute(w, chi2w, enc, need,
-                                 cenc ? 0.0 : direction_lb(need, chi2m, est, lsx && need0 && (e2w <= P.e2_cut || P.cut_guard_k > 0.0), c5x,
-                                                          e2w <= P.e2_cut ? ddx : P.cut_guard_k * ddx));
+                                 guarded_lb(P, need, chi2m, est, lsx && need0, e2w > P.e2_cut, cenc, c5x, ddx));
             }
 #ifdef RVM_PROFILE
             prof_dec(rt_arr, nl - 1);
@@ -1304,153 +1169,52 @@ void logl_kernel(const DevPlan P, const int W,
         return;
     }
 #ifdef RVM_PROFILE
-    PROF_T(t_end);
-    const int gw = (blockIdx.y * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + wv;
-    if (lane == 0 && gw < RVM_PROF_MAX_WAVES) {
-        unsigned long long* o = rvm_prof + (size_t)gw * RVM_PROF_SLOTS;
-        o[0] = t_start;
-        o[1] = t_pro;
-        o[2] = t_seg;
-        o[3] = t_epo;
-        o[4] = t_end;
-        o[5] = rt_start;
-        o[6] = __builtin_amdgcn_s_memrealtime();
-        o[7] = (unsigned long long)lvl | ((unsigned long long)blockIdx.y << 8) | ((unsigned long long)mult << 16);
-        o[8] = (unsigned long long)redo;
-        o[9] = (unsigned long long)E;
-        o[10] = (unsigned long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_REG_HW_ID
-        o[14] = t_p1;
-        o[15] = t_p2;
-        o[16] = t_p3;
-        o[17] = t_p4;
-    }
+    prof_write((blockIdx.y * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + wv,
+               (unsigned long long)lvl | ((unsigned long long)blockIdx.y << 8) | ((unsigned long long)mult << 16), nullptr);
 #endif
 }
 
-// Dynamic-LDS budget of one logl_kernel instantiation on the current device: the CU's 160 KB minus
-// the kernel's own static LDS (hipFuncGetAttributes; ~28 KB), with the attribute that admits a
-// dynamic request beyond 64 KB set once per device and instantiation.
+// Dynamic-LDS budget of one instantiation (lds_budget); where the attribute could not be set, what the
+// default 64 KB leaves beside the kernel's static LDS, and 32 KB if the runtime cannot tell
 template <int NPV, bool D3V, bool DECV>
-static size_t lds_budget() {
-    static size_t budget[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-        (void)hipGetLastError();
-        return 32 * 1024;
-    }
-    if (budget[dev] == 0) {
-        const void* f = reinterpret_cast<const void*>(&logl_kernel<NPV, D3V, DECV>);
+static size_t logl_budget() {
+    if (const size_t b = lds_budget<&logl_kernel<NPV, D3V, DECV>>()) return b;
+    static const size_t fallback = [] {  // (asked once: the kernel's static LDS is the same on every device)
         hipFuncAttributes fa{};
-        size_t b = 32 * 1024;  // (conservative if the runtime cannot tell)
-        if (hipFuncGetAttributes(&fa, f) == hipSuccess && fa.sharedSizeBytes < (size_t)RVM_LDS_PER_CU) {
-            const size_t lim = (size_t)RVM_LDS_PER_CU - fa.sharedSizeBytes;
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lim) == hipSuccess)
-                b = lim;
-            else if (fa.sharedSizeBytes < 64 * 1024)
-                b = 64 * 1024 - fa.sharedSizeBytes;
-        }
+        const void* f = reinterpret_cast<const void*>(&logl_kernel<NPV, D3V, DECV>);
+        const bool ok = hipFuncGetAttributes(&fa, f) == hipSuccess && fa.sharedSizeBytes < 64 * 1024;
         (void)hipGetLastError();
-        budget[dev] = b;
-    }
-    return budget[dev];
+        return ok ? (size_t)64 * 1024 - fa.sharedSizeBytes : (size_t)32 * 1024;
+    }();
+    return fallback;
 }
 
+// The launch: the layout is choose_logl_layout's (rvm_plan_host.cpp), whole
 template <int NPV, bool D3V>
 static hipError_t launch_logl_t(const DevPlan& P, int W, const double* params, double hill_factor,
                                 unsigned long long* slots, double* logl, int32_t* status, double* rv_out,
                                 const StretchArgs& sa, hipStream_t stream, int* dry_blocks) {
-    const int lpw = LanesPerWalker<NPV>::value;
-    const int wpb = 64 / lpw;
-    const int groups = (W + wpb - 1) / wpb;
-    // one walker group per block while the blocks fit one per CU (every wave alone on its SIMD:
-    // latency-bound); beyond that two groups with mirrored level order per block, which pairs
-    // the heaviest level with the lightest on each SIMD (logl_kernel)
-    // Paired one-group blocks (3 planets, round 6): where two groups would share a block, a launch of
-    // at most one group per CU instead runs one group per block with the extension as its fifth wave
-    // (cx below), two such blocks per CU (the 3-planet instantiation is held to 168 VGPRs for it) --
-    // the extension beside the main pass instead of after it, for config 5's 4096-walker half-steps.
-    // (A/B knob RVM_CX_PAIRS=0: the two-group blocks)
+    // (A/B knob RVM_CX_PAIRS=0: two-group blocks instead of the paired one-group blocks)
     static const bool pairs_env = [] {
         const char* e = getenv("RVM_CX_PAIRS");
         return !(e && e[0] == '0');
     }();
-    const bool pairs = NPV == 3 && !D3V && pairs_env && P.ext_mult > 0 && rv_out == nullptr && P.n_cu > 0 &&
-                       2 * groups > P.n_cu && groups <= P.n_cu && W >= RVM_CX_MIN_WALKERS;
-    const int G = (!pairs && P.n_cu > 0 && 2 * groups > P.n_cu && 2 * P.n_levels * 64 <= 512) ? 2 : 1;
-    dim3 grid((groups + G - 1) / G, 2);
-    // one group per block (the blocks fit one per CU): the extension level as an extra wave
-    // (logl_kernel, cx) when the plan has one and no model RVs are asked for.  The fifth wave shares
-    // SIMD 0 with level 0 (4 + 8 steps per base step against level 3's 7 alone), which costs every
-    // launch ~60 % (config 1's one-walker launch 0.335 -> 0.538 ms with nothing flagged,
-    // scripts/probe/config1_probe.py): worth it only where a launch almost surely holds a flagged
-    // walker.  Launches of a few walkers (the reference API's single-state calls) run the extension
-    // after the main pass, only when flagged -- the same bits either way.
-    const bool cx = G == 1 && P.ext_mult > 0 && rv_out == nullptr && W >= RVM_CX_MIN_WALKERS;
-    dim3 block(64 * (P.n_levels + (cx ? 1 : 0)) * G);
-    const int emax = P.fwd.n_epochs > P.bwd.n_epochs ? P.fwd.n_epochs : P.bwd.n_epochs;
-    const size_t rows = (size_t)(D3V ? 7 : 5) * NPV;
     const bool fused = sa.c != nullptr || sa.mh_scale != nullptr;
-    const size_t init = P.rmax > 0 ? (size_t)RVM_INIT_DOUBLES * sizeof(double) : 0;  // per group / unit
-    // (+ the LDS-coupled layout's ring of the levels' star vx per group, logl_kernel lring)
-    const size_t lc_ring = (size_t)P.lc_ring * (P.n_levels + 1) * wpb * sizeof(double);
-    size_t smem = (size_t)emax * 4 * sizeof(double) + (fused ? (rows + 3) * G * wpb * sizeof(double) : 0) + G * init +
-                  G * lc_ring;
-    // level-split layout (logl_kernel) when it lowers the heaviest SIMD's load: in steps per base
-    // step, max(m3, m2 + m0, 2 m1) for one round of <= n_cu blocks, against m3 per round of
-    // single-group blocks or max_i(m_i + m_{n-1-i}) per round of two-group blocks
-    int nA = 0, tB = 8, splitA = 0, lsx = 0;
-    // with the adaptive resolution's extension level: where two groups would share a block (no
-    // room for the concurrent extension wave), the level-split layout carries the extension as a
-    // fifth level of the main pass (logl_kernel, lsx) -- the ring then holds whole directions
-    if (P.lv_rv != nullptr && W <= P.lv_stride && P.n_levels == 4 && P.n_cu > 0 && P.ext_mult > 0 &&
-        rv_out == nullptr && G == 2 && emax <= RVM_LS_RING) {
-        const int units = 2 * groups;
-        const int na = groups, nb = (units + 7) / 8;
-        const size_t smem_x = (size_t)emax * 8 * sizeof(double) + (size_t)8 * emax * wpb * sizeof(double) + 2 * init;
-        if (na + nb <= P.n_cu && smem_x <= lds_budget<NPV, D3V, true>()) {
-            nA = na;
-            tB = 8;
-            lsx = 1;
-            grid = dim3(na + nb, 1);
-            block = dim3(8 * 64);
-            smem = smem_x;
-        }
-    }
-    if (nA == 0 && P.lv_rv != nullptr && W <= P.lv_stride && P.n_levels == 4 && P.n_cu > 0) {
-        const int* m = P.mult;
-        const int units = 2 * groups;
-        // type-B blocks carry 6 units' level 1 (two of them split head / tail) when the CUs allow,
-        // else 8
-        const int na = groups;
-        tB = na + (units + 5) / 6 <= P.n_cu ? 6 : 8;
-        const int nb = (units + tB - 1) / tB;
-        const int c_dec = std::max(m[3], std::max(m[2] + m[0], 2 * m[1]));
-        const int c_cpl = G == 1 ? m[3] * ((2 * groups + P.n_cu - 1) / P.n_cu)
-                                 : std::max(m[0] + m[3], m[1] + m[2]) * ((groups + P.n_cu - 1) / P.n_cu);
-        const int ring = emax < RVM_LS_RING ? emax : RVM_LS_RING;
-        const size_t smem_ls =
-            (size_t)emax * 8 * sizeof(double) + (size_t)6 * ring * wpb * sizeof(double) + 2 * init;
-        if (na + nb <= P.n_cu && c_dec < c_cpl && smem_ls <= lds_budget<NPV, D3V, true>()) {
-            nA = na;
-            grid = dim3(na + nb, 1);
-            block = dim3(8 * 64);
-            // level 0 split head / tail in the type-A blocks: the combiner starts with the head's
-            // hand-off, so the ring must hold every epoch of a direction
-            splitA = emax <= RVM_LS_RING ? 1 : 0;
-            smem = smem_ls;
-        }
-    }
+    const LoglLayout Y = choose_logl_layout(P, W, rv_out != nullptr, fused, pairs_env, logl_budget<NPV, D3V, false>(),
+                                            logl_budget<NPV, D3V, true>());
     if (dry_blocks != nullptr) {  // (the grid this launch would take, nothing launched: run_logl's hedge)
-        *dry_blocks = (int)(grid.x * grid.y);
+        *dry_blocks = (int)(Y.grid_x * Y.grid_y);
         return hipSuccess;
     }
-    if (nA > 0) {
-        logl_kernel<NPV, D3V, true><<<grid, block, smem, stream>>>(P, W, params, hill_factor, slots, rv_out, logl,
-                                                                   status, sa, nA, tB | (splitA << 8) | (lsx << 9));
+    const dim3 grid(Y.grid_x, Y.grid_y), block(Y.block);
+    if (Y.nA > 0) {
+        logl_kernel<NPV, D3V, true><<<grid, block, Y.smem, stream>>>(P, W, params, hill_factor, slots, rv_out, logl,
+                                                                     status, sa, Y.nA,
+                                                                     Y.tB | (Y.splitA << 8) | (Y.lsx << 9));
     } else {
-        if (smem > lds_budget<NPV, D3V, false>()) return hipErrorInvalidConfiguration;
-        logl_kernel<NPV, D3V, false><<<grid, block, smem, stream>>>(P, W, params, hill_factor, slots, rv_out, logl,
-                                                                    status, sa, nA, 8);
+        if (!Y.fits) return hipErrorInvalidConfiguration;
+        logl_kernel<NPV, D3V, false><<<grid, block, Y.smem, stream>>>(P, W, params, hill_factor, slots, rv_out, logl,
+                                                                      status, sa, 0, 8);
     }
     return hipGetLastError();
 }
@@ -1461,33 +1225,21 @@ static hipError_t launch_logl_t(const DevPlan& P, int W, const double* params, d
 // staging, the adaptive resolution's t = 0 state): the fallback every launch may take, so a plan whose
 // schedule it cannot stage is refused at creation rather than failing its launches
 static size_t logl_smem_worst(const DevPlan& P, int npv, bool d3) {
-    const int wpb = 64 / (npv == 1 ? 1 : (npv == 2 ? 2 : 4));
     const int emax = P.fwd.n_epochs > P.bwd.n_epochs ? P.fwd.n_epochs : P.bwd.n_epochs;
-    const size_t rows = (size_t)(d3 ? 7 : 5) * npv;
-    const size_t init = P.rmax > 0 ? (size_t)RVM_INIT_DOUBLES * sizeof(double) : 0;
-    const size_t ring = (size_t)P.lc_ring * (P.n_levels + 1) * wpb * sizeof(double);
-    return (size_t)emax * 4 * sizeof(double) + (rows + 3) * 2 * wpb * sizeof(double) + 2 * init + 2 * ring;
+    return LoglLds::coupled(emax, walkers_per_group(npv), 2, (d3 ? 7 : 5) * npv, true, P.rmax > 0, P.lc_ring, P.n_levels)
+        .bytes();
 }
 
 hipError_t prepare_logl(const DevPlan& P) {
     const bool inc = P.inclined != 0;
     size_t budget = 0;
-#define RVM_PREP(NPV)                                                                          \
-    (inc ? ((void)lds_budget<NPV, true, true>(), budget = lds_budget<NPV, true, false>())      \
-         : ((void)lds_budget<NPV, false, true>(), budget = lds_budget<NPV, false, false>()))
+#define RVM_PREP(NPV)                                                                              \
+    case NPV:                                                                                      \
+        budget = inc ? ((void)logl_budget<NPV, true, true>(), logl_budget<NPV, true, false>())     \
+                     : ((void)logl_budget<NPV, false, true>(), logl_budget<NPV, false, false>());  \
+        break;
     switch (P.n_planets) {
-        case 1:
-            (void)RVM_PREP(1);
-            break;
-        case 2:
-            (void)RVM_PREP(2);
-            break;
-        case 3:
-            (void)RVM_PREP(3);
-            break;
-        case 4:
-            (void)RVM_PREP(4);
-            break;
+        RVM_PREP(1) RVM_PREP(2) RVM_PREP(3) RVM_PREP(4)
         default:
             return hipErrorInvalidValue;
     }
@@ -1503,25 +1255,12 @@ hipError_t launch_logl(const DevPlan& P, int W, const double* params, double hil
                        int* dry_blocks) {
     const bool inc = P.inclined != 0;
     hipError_t e = hipErrorInvalidValue;
-#define RVM_LAUNCH(NPV) \
-    (inc ? launch_logl_t<NPV, true>(P, W, params, hill_factor, slots, logl, status, rv_out, sa, stream, dry_blocks) \
-         : launch_logl_t<NPV, false>(P, W, params, hill_factor, slots, logl, status, rv_out, sa, stream, dry_blocks))
-    switch (P.n_planets) {
-        case 1:
-            e = RVM_LAUNCH(1);
-            break;
-        case 2:
-            e = RVM_LAUNCH(2);
-            break;
-        case 3:
-            e = RVM_LAUNCH(3);
-            break;
-        case 4:
-            e = RVM_LAUNCH(4);
-            break;
-        default:
-            break;
-    }
+#define RVM_LAUNCH(NPV)                                                                                                   \
+    case NPV:                                                                                                             \
+        e = inc ? launch_logl_t<NPV, true>(P, W, params, hill_factor, slots, logl, status, rv_out, sa, stream, dry_blocks)  \
+                : launch_logl_t<NPV, false>(P, W, params, hill_factor, slots, logl, status, rv_out, sa, stream, dry_blocks); \
+        break;
+    switch (P.n_planets) { RVM_LAUNCH(1) RVM_LAUNCH(2) RVM_LAUNCH(3) RVM_LAUNCH(4) }
 #undef RVM_LAUNCH
     return e;
 }

@@ -250,6 +250,81 @@ bool plan_wants_level_split(const DevPlan& P, int32_t max_walkers, const PlanKno
     return inc && P.n_cu > 0 && 2 * groups > P.n_cu;
 }
 
+LoglLayout choose_logl_layout(const DevPlan& P, int W, bool want_rv, bool fused, bool cx_pairs, size_t budget_lc,
+                              size_t budget_ls) {
+    const int wpb = walkers_per_group(P.n_planets);
+    const int groups = (W + wpb - 1) / wpb;
+    const int nl = P.n_levels, n_cu = P.n_cu;
+    const int emax = std::max(P.fwd.n_epochs, P.bwd.n_epochs);
+    const bool init = P.rmax > 0;
+    // the extension level can run beside the main pass: the plan has one, and no model RVs are asked for
+    const bool xcon = P.ext_mult > 0 && !want_rv;
+    const bool crowded = n_cu > 0 && 2 * groups > n_cu;  // one group per block would not fit one block per CU
+    // One walker group per block while the blocks fit one per CU (every wave alone on its SIMD: latency-bound);
+    // beyond that two groups with mirrored level order per block, which pairs the heaviest level with the
+    // lightest on each SIMD.  Paired one-group blocks (3 planets, planar): where two groups would share a block,
+    // a launch of at most one group per CU instead runs one group per block with the extension as its fifth wave
+    // (cx), two such blocks per CU (that instantiation is held to 168 VGPRs for it) -- the extension beside the
+    // main pass instead of after it, for 4096-walker half-steps.  (A/B knob RVM_CX_PAIRS=0: cx_pairs false)
+    const bool pairs = P.n_planets == 3 && !P.inclined && cx_pairs && xcon && crowded && groups <= n_cu &&
+                       W >= RVM_CX_MIN_WALKERS;
+    LoglLayout Y{};
+    Y.G = !pairs && crowded && 2 * nl * 64 <= 512 ? 2 : 1;
+    // One group per block: the extension level as an extra wave (cx).  The fifth wave shares SIMD 0 with level 0
+    // (4 + 8 steps per base step against level 3's 7 alone), which costs every launch ~60 % (a one-walker launch
+    // 0.335 -> 0.538 ms with nothing flagged, scripts/probe/config1_probe.py): worth it only where a launch almost
+    // surely holds a flagged walker.  Launches of a few walkers run the extension after the main pass, only when
+    // flagged -- the same bits either way.
+    Y.cx = Y.G == 1 && xcon && W >= RVM_CX_MIN_WALKERS ? 1 : 0;
+    Y.tB = 8;
+    Y.grid_x = (unsigned)((groups + Y.G - 1) / Y.G);
+    Y.grid_y = 2;
+    Y.block = (unsigned)(64 * (nl + Y.cx) * Y.G);
+    Y.lds = LoglLds::coupled(emax, wpb, Y.G, (P.inclined ? 7 : 5) * P.n_planets, fused, init, P.lc_ring, nl);
+    // Level-split layout (logl_kernel): one round of na type-A and nb type-B blocks, one per CU
+    const bool can_split = P.lv_rv != nullptr && W <= P.lv_stride && nl == 4 && n_cu > 0;
+    const int units = 2 * groups, na = groups;
+    auto split = [&](int tB, int nb, const LoglLds& lds) {
+        Y.nA = na;
+        Y.nB = nb;
+        Y.tB = tB;
+        Y.grid_x = (unsigned)(na + nb);
+        Y.grid_y = 1;
+        Y.block = 8 * 64;
+        Y.lds = lds;
+    };
+    // ... with the extension level: where two groups would share a block (no room for the concurrent extension
+    // wave), it carries the extension as a fifth level of the main pass (lsx) -- the ring holds whole directions
+    if (can_split && xcon && Y.G == 2 && emax <= RVM_LS_RING) {
+        const int nb = (units + 7) / 8;
+        const LoglLds lds = LoglLds::level_split(emax, wpb, 4, init);
+        if (na + nb <= n_cu && lds.bytes() <= budget_ls) {
+            split(8, nb, lds);
+            Y.lsx = 1;
+        }
+    }
+    // ... else when it lowers the heaviest SIMD's load: in steps per base step, max(m3, m2 + m0, 2 m1) for one
+    // round of <= n_cu blocks, against m3 per round of one-group or max_i(m_i + m_{n-1-i}) of two-group blocks
+    if (Y.nA == 0 && can_split) {
+        const int32_t* m = P.mult;
+        // type-B blocks carry 6 units' level 1 (two of them split head / tail) when the CUs allow, else 8
+        const int tB = na + (units + 5) / 6 <= n_cu ? 6 : 8;
+        const int nb = (units + tB - 1) / tB;
+        const int c_dec = std::max(m[3], std::max(m[2] + m[0], 2 * m[1]));
+        const int c_cpl = Y.G == 1 ? m[3] * ((2 * groups + n_cu - 1) / n_cu)
+                                   : std::max(m[0] + m[3], m[1] + m[2]) * ((groups + n_cu - 1) / n_cu);
+        const LoglLds lds = LoglLds::level_split(emax, wpb, 3, init);
+        if (na + nb <= n_cu && c_dec < c_cpl && lds.bytes() <= budget_ls) {
+            split(tB, nb, lds);
+            // (level 0 split head / tail: the combiner starts with the head's hand-off)
+            Y.splitA = emax <= RVM_LS_RING ? 1 : 0;
+        }
+    }
+    Y.smem = Y.lds.bytes();
+    Y.fits = Y.nA > 0 || Y.smem <= budget_lc;
+    return Y;
+}
+
 // the next sub-range of a block: its offset, the block's running size `end` moved past it
 static size_t take(size_t& end, size_t bytes) {
     end += bytes;

@@ -61,6 +61,24 @@ void fill_plan_extension(DevPlan* P);
 // the level-split layout's condition (four strictly increasing levels, a largest launch of two-group blocks)
 bool plan_wants_level_split(const DevPlan& P, int32_t max_walkers, const PlanKnobs& K);
 
+// The layout one likelihood launch takes (rvm_logl.hip launch_logl_t launches exactly this):
+//   LDS-coupled (nA = 0): 2-D grid of blocks of G = 1 or 2 walker groups, one wave per level (G = 2: the second
+//     group's levels mirrored), with cx the extension level as a further wave (G = 1 only);
+//   level-split (nA > 0; four levels, W <= lv_stride): 1-D grid of 8-wave blocks, nA of type A and nB of type B
+//     carrying tB (6 or 8) units each; splitA: level 0 split head / tail, lsx: the extension as a fifth level --
+//     both need a whole direction in the ring (emax <= RVM_LS_RING).  smem = lds.bytes(); fits: within budget.
+struct LoglLayout {
+    int G, cx, nA, nB, tB, splitA, lsx;
+    unsigned grid_x, grid_y, block;
+    LoglLds lds;
+    size_t smem;
+    bool fits;
+};
+// The whole decision, from the plan's scalars (its pointers only tested against null), the launch's (W, model RVs
+// asked for, a fused sampler step), the RVM_CX_PAIRS knob and the two instantiations' dynamic-LDS budgets.
+LoglLayout choose_logl_layout(const DevPlan& P, int W, bool want_rv, bool fused, bool cx_pairs, size_t budget_lc,
+                              size_t budget_ls);
+
 // Byte offsets inside the plan's device blocks, in the order they are laid out; `bytes` the block's size.
 struct DmemLayout {  // schedule f64 | slots | counters (u64) | schedule int32, + 64
     size_t seg_h1[2], obs_rv[2], obs_s2[2], slots, counters, seg_n[2], obs_idx[2], bytes;

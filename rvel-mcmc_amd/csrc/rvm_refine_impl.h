@@ -57,6 +57,7 @@
 // round identically here)
 #pragma clang fp contract(on)
 
+#include "rvm_launch.h"
 #include "rvm_walker.h"
 
 // The halving passes integrate with the fourth-order Kepler guess (segment_gated's default, KG = 0): the
@@ -204,23 +205,6 @@ struct DirState {
     int open;
     double chi, lb, pest, best, bchi;
 };
-
-// The Richardson combiner of one epoch for one walker: from the levels' star vx (lv[q * 64], level q's value
-// in the LDS row of this lane) the extrapolated RV, the RV without the coarsest level, and the epoch's
-// terms of chi2 and of the extrapolation-error estimate against the observation ob of variance s2.
-// side_pass's; refine_kernel's epoch loop still writes these expressions out itself, because its register
-// allocation is pinned by a test and this call moved it -- a change to one
-// is a change to both.
-__device__ __forceinline__ void combine_epoch(const DevPlan& P, const int nl, const double* lv, const double ob,
-                                              const double s2, double& rvx, double& rv3, double& dc2, double& de2) {
-    rvx = 0.0;
-    rv3 = 0.0;
-    for (int q = 0; q < nl; q++) rvx += P.lw[q] * lv[q * 64];
-    for (int q = 1; q < nl; q++) rv3 += P.lw3[q] * lv[q * 64];
-    const double r = rvx - ob;
-    dc2 = (r * r) / s2;
-    de2 = fabs((rvx - rv3) * (r + (rv3 - ob))) / s2;
-}
 
 // NW: waves per workgroup.  8 (512 threads) runs a both-direction group's two directions side by side
 // (mirrored levels) and plans of up to 8 levels; 4 (256 threads, plans of at most four levels) runs
@@ -1447,8 +1431,10 @@ __device__ __forceinline__ int side_pass(const DevPlan& P, const DirSched& SR, L
         __syncthreads();
         if (m.cancel[e & 1]) return 1;
         if (cmb) {
-            double rvx, rv3, dc2, de2;
-            combine_epoch(P, nl, &m.rv[e & 1][0][lane], SR.obs_rv[e], SR.obs_s2[e], rvx, rv3, dc2, de2);
+            double rvx, rv3, dc2, de2, s5;
+            const double* lv = &m.rv[e & 1][0][lane];  // (level q's value in the LDS row of this lane)
+            combine_epoch(P, nl, [&](int q) { return lv[q * 64]; }, SR.obs_rv[e], SR.obs_s2[e], rvx, rv3, dc2, de2, false,
+                          s5);
             c2 += dc2;
             e2 += de2;
             __hip_atomic_store(rvo + (size_t)e * stride, (unsigned long long)__double_as_longlong(rvx), __ATOMIC_RELAXED,
@@ -1852,34 +1838,7 @@ __global__ __launch_bounds__(256) void hedge_kernel(const DevPlan P, const int W
     if (ended) count_marked();
 }
 
-// The dynamic LDS a kernel of this file may request on the current device: all the CU has left beside the
-// kernel's static LDS, with the attribute admitting it set once per device and kernel; 0 when that could
-// not be done.  rvm_plan_create calls it for the plan's kernels (prepare_refine), so a launch never changes
-// function attributes -- launches stay capturable -- and a plan whose schedule would not fit is refused
-// there, not at launch.
-template <auto Kernel>
-static size_t lds_budget() {
-    static size_t budget[64] = {};
-    static bool known[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    if (!known[dev]) {
-        const void* f = reinterpret_cast<const void*>(Kernel);
-        hipFuncAttributes fa{};
-        size_t b = 0;
-        if (hipFuncGetAttributes(&fa, f) == hipSuccess && fa.sharedSizeBytes < (size_t)RVM_LDS_PER_CU) {
-            const size_t lim = (size_t)RVM_LDS_PER_CU - fa.sharedSizeBytes;
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lim) == hipSuccess) b = lim;
-        }
-        (void)hipGetLastError();
-        budget[dev] = b;
-        known[dev] = true;
-    }
-    return budget[dev];
-}
+// (the dynamic LDS a kernel may request: lds_budget, rvm_launch.h)
 // the hedge kernel's request: the whole remainder (no other block then shares its CU); 0: it cannot run
 template <int NPV, bool D3V>
 static size_t hedge_budget() {

@@ -107,6 +107,79 @@ __device__ __forceinline__ void segment_gated(Lane<NP>& s, KickPrep<NP>& kp, dou
         segment<8, false, D3, NP, L, KG, ACC>(s, kp, h, ns, unused);
 }
 
+// The speculation back-off of a wave (wave-uniform; fresh: {0, 4}): segments left to run gated after a redo, and
+// the next back-off -- doubled by each redo up to 64, back to 4 after a clean speculative segment.  A head hands
+// it to its tail as one LDS word: as two members there it moved the level-split instantiations' registers
+// (3 planets 170 -> 204 VGPRs).
+struct SpecState {
+    int off, bo;
+    __device__ __forceinline__ int pack() const { return off | (bo << 16); }
+    __device__ __forceinline__ static SpecState unpack(int w) { return SpecState{w & 0xFFFF, w >> 16}; }
+};
+// One segment of a level with the Stumpff series length nt; spec (implies nt <= 6): speculate unless a recent
+// segment of this wave needed a redo -- walkers whose orbits keep needing the general solver then run gated for
+// a while instead of paying for redos; the same bits either way.  (The extension's; the main loop of
+// rvm_logl.hip writes the same text out -- a change to one is a change to both.)
+template <bool D3, int NP, int L, int KG = 0>
+__device__ __forceinline__ void segment_backoff(Lane<NP>& s, KickPrep<NP>& kp, double h, int ns, int nt, bool spec,
+                                                SpecState& st, int& redo) {
+    if (spec) {
+        if (st.off == 0) {
+            if (segment<6, true, D3, NP, L, KG>(s, kp, h, ns, redo)) {
+                st.off = st.bo;
+                st.bo = st.bo < 64 ? 2 * st.bo : 64;
+            } else {
+                st.bo = 4;
+            }
+        } else {
+            segment<6, false, D3, NP, L, KG>(s, kp, h, ns, redo);
+            st.off--;
+        }
+    } else {
+        segment_gated<D3, NP, L, KG>(s, kp, h, ns, nt);
+    }
+}
+// A lane's eight dynamic doubles to and from rows of 64 doubles (o: the lane's entry of row 0): the t = 0 state,
+// a head's hand-off to its tail.  encm stays with the caller (zeroed, or handed over as a wave-uniform word).
+template <int NP>
+__device__ __forceinline__ void lane_save(const Lane<NP>& s, double* o) {
+    o[0] = s.rx;
+    o[64] = s.ry;
+    o[128] = s.vx;
+    o[192] = s.vy;
+    o[256] = s.rz;
+    o[320] = s.vz;
+    o[384] = s.r;
+    o[448] = s.ir;
+}
+template <int NP>
+__device__ __forceinline__ void lane_load(Lane<NP>& s, const double* in) {
+    s.rx = in[0];
+    s.ry = in[64];
+    s.vx = in[128];
+    s.vy = in[192];
+    s.rz = in[256];
+    s.vz = in[320];
+    s.r = in[384];
+    s.ir = in[448];
+}
+// One direction's epoch schedule as staged in LDS: [E] seg_h1 | [E] obs_rv | [E] obs_s2 | [E] (seg_n, obs_idx)
+struct SchedView {
+    double *len, *rv, *s2;
+    int *n, *idx;
+    __device__ __forceinline__ SchedView(double* b, int E)
+        : len(b), rv(b + E), s2(b + 2 * E), n(reinterpret_cast<int*>(b + 3 * E)), idx(n + E) {}
+};
+__device__ __forceinline__ void stage_sched(const DirSched& S, const SchedView& v, int i0, int stride) {
+    for (int i = i0; i < S.n_epochs; i += stride) {  // (epochs i0, i0 + stride, ... of S into its view)
+        v.len[i] = S.seg_h1[i];
+        v.rv[i] = S.obs_rv[i];
+        v.s2[i] = S.obs_s2[i];
+        v.n[i] = S.seg_n[i];
+        v.idx[i] = S.obs_idx[i];
+    }
+}
+
 // kernel parameter row r of walker w: from the SoA input, or (fused sampler step) the row's fixed
 // value or the walker's proposal of the free parameter feeding it: MH (sa.mh_scale), or stretch
 // (kind 1 / 2: half 1's walker of a speculative iteration against its partner's rejected /
@@ -280,6 +353,28 @@ struct SpinClock {
         return __builtin_amdgcn_s_memrealtime() - last > ticks;
     }
 };
+// The bounded wait on another wave's progress: polls progress() (an int >= 0, wave-uniform) every s_sleep SLEEP
+// until done(progress); the clock restarts whenever the value moves, `ticks` without a move gives up (returns
+// true).  The level-split layout's waits on LDS counters; the LDS-coupled layouts' two write the same loop out
+// (rvm_logl.hip lc_wait: the call cost the 3-planet paired layout time).  The level-split combiner's polls of
+// the HBM-handed values keep their own shape on purpose (a straight-line first test, a bottom-tested loop: the
+// compiler then does not wait for every prefetched load in flight).
+template <int SLEEP, typename Progress, typename Done>
+__device__ __forceinline__ bool wait_progress(SpinClock& clk, unsigned long long ticks, Progress&& progress,
+                                              Done&& done) {
+    int seen = -1;
+    for (;;) {
+        const int p = progress();
+        if (done(p)) return false;
+        if (p != seen) {
+            seen = p;
+            clk.restart();
+        } else if (clk.expired(ticks)) {
+            return true;
+        }
+        __builtin_amdgcn_s_sleep(SLEEP);
+    }
+}
 
 // A gated segment (segment_gated) that a partner can stop part-way: the work a team B or an eager
 // block does speculatively (rvm_refine.hip) is cancelled through a word that reaches `tag`.  Polled
@@ -381,6 +476,85 @@ __device__ __forceinline__ int dir_status(int enc, bool open, double chi2) {
 __device__ __forceinline__ double open_lb(double chi2, double d, double est_raw) {
     const double b = chi2 - fmin(d, RVM_CUT_EST_FACTOR * est_raw);
     return b > 0.0 ? b : 0.0;  // (NaN -> 0)
+}
+
+// ---- the adaptive resolution's rules after the main pass, one statement each (oracle/rvoracle.c) ----
+// The Richardson combiner of one epoch for one walker: from the levels' star vx (lv(q), level q's value) the
+// extrapolated RV, the RV without the coarsest level, and the epoch's terms of chi2 and of the error estimate
+// against the observation ob of variance s2; with want5, s5 = the extension's partial sum over the main pass's
+// levels.  Ascending q from 0.0, rv3 from q = 1, each term one expression: the bits rest on it (fp contract).
+// The likelihood kernel's combiners and side_pass call this; refine_kernel's epoch loop writes these expressions
+// out itself -- its register allocation is pinned by a test and the call moved it (DESIGN.md section 10 item
+// 10): a change to one is a change to both.
+template <typename Lv>
+__device__ __forceinline__ void combine_epoch(const DevPlan& P, const int nl, Lv&& lv, const double ob,
+                                              const double s2, double& rvx, double& rv3, double& dc2, double& de2,
+                                              const bool want5, double& s5) {
+    rvx = 0.0;
+    rv3 = 0.0;
+    for (int q = 0; q < nl; q++) rvx += P.lw[q] * lv(q);
+    for (int q = 1; q < nl; q++) rv3 += P.lw3[q] * lv(q);
+    const double r = rvx - ob;
+    dc2 = (r * r) / s2;
+    de2 = fabs((rvx - rv3) * (r + (rv3 - ob))) / s2;
+    if (want5) {
+        s5 = 0.0;
+        for (int q = 0; q < nl; q++) s5 += P.lw5[q] * lv(q);
+    }
+}
+// The extension's sums at one epoch: r5 = all nl + 1 levels (s5 the main pass's partial sum, vx the extension
+// level's value of weight w5), its chi2 term dc5 and the term dd5 of its change against the main pass's RV r.
+__device__ __forceinline__ void extension_epoch(const double s5, const double w5, const double vx, const double r,
+                                                const double ob, const double s2, double& r5, double& dc5,
+                                                double& dd5) {
+    r5 = s5 + w5 * vx;
+    const double q = r5 - ob;
+    dc5 = (q * q) / s2;
+    dd5 = fabs((r5 - r) * (q + (r - ob))) / s2;
+}
+// One level's flag word as it joins the walker's (OR them): on an adaptive plan an encounter that a level other
+// than the finest (DevPlan::fin_level) sees moves to RVM_ENC_COARSE.  (Values: references cost scratch.)
+#define RVM_ENC_COARSE 0x100
+__device__ __forceinline__ int level_flags(const int f, const bool fin, const bool adaptive) {
+    return fin || !adaptive ? f : (f & ~1) | ((f & 1) ? RVM_ENC_COARSE : 0);
+}
+// ... an encounter only the coarser levels saw: the direction refines instead (`cenc`)
+__device__ __forceinline__ bool coarse_only_encounter(const int encs) {
+    return (encs & RVM_ENC_COARSE) != 0 && (encs & 1) == 0;
+}
+// A direction stays open after the main pass (dir_main `bad`): no flag, and its estimate above the bound, a
+// non-finite chi2 or estimate, the walker past the eccentricity guard (e2), or a coarse-only encounter.
+__device__ __forceinline__ bool direction_open(const DevPlan& P, const int enc, const double chi2, const double est,
+                                               const double e2, const bool cenc) {
+    return enc == 0 && (est / P.npoints > P.rtol_dir || !isfinite(chi2) || !isfinite(est) ||
+                        (P.ext_mult > 0 && e2 > P.e2_guard) || cenc);
+}
+// The extension's verdict on an open direction: 2 its own encounter (xenc) ends the walker ENCOUNTER, 1 a change
+// dd within RVM_EXT_ACCEPT rtol_dir npoints settles it (false for a non-finite one) -- either way its chi2 is
+// the extension's --, 0 it stays open.  coarse_blocks: a coarse-only encounter keeps the change from settling
+// it; cx and lsx pass their cenc, extend_pass passes false -- it has no such test.
+__device__ __forceinline__ int extension_verdict(const DevPlan& P, const bool xenc, const double dd,
+                                                 const bool coarse_blocks) {
+    if (xenc) return 2;
+    return !coarse_blocks && dd <= RVM_EXT_ACCEPT * P.rtol_dir * P.npoints ? 1 : 0;
+}
+// A direction's lower bound on its chi2 after the main pass and the extension (oracle/rvoracle.c dir_extend): 0
+// when settled; the extension's (xc5, its change xdd) when it ran and is finite, else the main pass's alone.
+__device__ __forceinline__ double direction_lb(const bool need, const double chi2_main, const double est_raw,
+                                               const bool xran, const double xc5, const double xdd) {
+    if (!need) return 0.0;
+    if (xran && isfinite(xc5) && isfinite(xdd)) return open_lb(xc5, xdd, est_raw);
+    return open_lb(chi2_main, INFINITY, est_raw);
+}
+// ... with the cut guard (DevPlan::e2_cut): past it (past_cut = e2 > e2_cut; e2 is never NaN, walker_setup
+// forms it with fmax from 0) the extension's bound counts only with cut_guard_k > 0, its change k-fold; a
+// coarse-only encounter (cenc) has no bound at all.
+__device__ __forceinline__ double guarded_lb(const DevPlan& P, const bool need, const double chi2_main,
+                                             const double est_raw, const bool xran, const bool past_cut,
+                                             const bool cenc, const double xc5, const double xdd) {
+    if (cenc) return 0.0;
+    return direction_lb(need, chi2_main, est_raw, xran && (!past_cut || P.cut_guard_k > 0.0), xc5,
+                        past_cut ? P.cut_guard_k * xdd : xdd);
 }
 
 // The sampler's accept inputs of walker slot wo of a fused launch (the certain-reject test):
