@@ -76,6 +76,7 @@ extern "C" {
 #define RVM_MAX_LEVELS 6
 #define RVM_MAX_EPOCHS_PER_DIRECTION 1700 /* epochs with t >= 0, and with t < 0, per plan */
 #define RVM_SMALA_MAX_PARAMS 20           /* free parameters per SMALA chain                 */
+#define RVM_MAX_QUANTILES 16              /* quantiles per rvm_rows_quantiles call           */
 #define RVM_RESOLVE_MAX_LIMIT 12          /* rvm_config.resolve_max                          */
 
 /* Integrator configuration of a plan. */
@@ -527,6 +528,57 @@ int rvm_chain_moments(const double* chain, int32_t n_params, int32_t n_cols, int
 size_t rvm_chain_autocov_workspace_bytes(int32_t n_params, int32_t n_cols, int32_t n_lags);
 int rvm_chain_autocov(const double* chain, const double* mean, int32_t n_params, int32_t n_cols, int64_t t0, int64_t t1,
                       int32_t lag0, int32_t n_lags, double* acov_out, void* workspace, void* stream);
+
+/* ---- posterior summaries of data already in device memory ------------------------------------------
+ * What the reference reads off its host chain (driver.py:265-333 return_trimmed_results, :335
+ * plot_corners): the parameters' quantiles and covariance, and states drawn from the chain whose RV
+ * curves make the credible band.  The conventions of the chain entry points hold for the three launch
+ * functions: device pointers (q is a host array, copied into the launch), no allocation, no
+ * synchronisation, stream-ordered and capturable, no floating-point atomics, the same bits from run to
+ * run; argument errors return < 0 before any HIP call and name the argument in rvm_last_error.  A
+ * workspace's contents are unspecified before and after a call.
+ *
+ * rows_quantiles: exact quantiles of n_rows rows of doubles.  Element (o, i) of row r is
+ *   x[r row_stride + o outer_stride + i], o < n_outer, i < n_inner (strides >= 0, in elements;
+ *   n_rows 1 .. 65535; n_outer n_inner <= 2^32 - 1, what the 32-bit counters hold).
+ *     a parameter of a chain over the steps [t0, t1): x = chain + t0 P W, n_rows = P, row_stride = W,
+ *       n_outer = t1 - t0, outer_stride = P W, n_inner = W;
+ *     the rows of an rv_out matrix [n_times][S]: n_outer = 1, n_inner = row_stride = S.
+ *   q: n_q = 1 .. RVM_MAX_QUANTILES values in [0, 1].  out[r][j], the quantile q[j] of row r, is
+ *     NaNs are not counted: m is the number of the row's other values (n_valid_out[r], nullable), and
+ *       v[0 .. m-1] those values in ascending order -- +-inf are ordinary values, -0 sorts before +0;
+ *     m = 0: NaN;  otherwise h = q (m - 1) (one rounded product), lo = floor(h), g = h - lo,
+ *       hi = min(lo + 1, m - 1), and
+ *     out = v[lo] if g == 0 or v[hi] == v[lo], else v[lo] + g (v[hi] - v[lo]) (the product rounded, then
+ *       the sum: no fused multiply-add) -- numpy's default 'linear' rule up to its last roundings.
+ *   The order statistics are exact: a radix select on the order-preserving 64-bit key of a double (all
+ *   bits of a negative flipped, the sign bit of the others), eight bits per pass; the row is not sorted
+ *   and not modified.  The loads are 16 bytes wide when x is 16-byte aligned and both strides are even.
+ *   workspace: rvm_rows_quantiles_workspace_bytes(n_rows, n_q) bytes (0 on bad arguments), 8-byte aligned.
+ * chain_cov, over the steps [t0, t1) of a chain [n_steps][n_params][n_cols], n = t1 - t0, W = n_cols:
+ *   cov_out[p][q] = (sum_w sum_t y_p y_q) / (double)(n W - 1),  y_p = x[t][p][w] - center[p] rounded at
+ *   use, center [n_params] on the device.  The order of the sum is rvm_chain_autocov's: per walker, t
+ *   ascending in one thread, acc = fma(y_p, y_q, acc) from acc = 0; the walkers of a block of 256 by the
+ *   binary tree (h = 128, 64, ..., 1; absent walkers add +0); the walker blocks in index order in a second
+ *   small launch; one division.  p >= q is computed and mirrored, so cov_out is symmetric bit for bit;
+ *   n W = 1 gives NaN; n_params <= 16384, n_cols <= 4194240.  workspace:
+ *   rvm_chain_cov_workspace_bytes(n_params, n_cols) bytes (8 n_params^2 n_cols, the walkers' own sums
+ *   between the two launches; 0 on bad arguments).
+ * chain_draw: n_samples states of the steps [t0, t1), with replacement.  Sample s takes (u1, u2) =
+ *   uniform2(seed, item = s, iteration = draw_id, stream 8), or draws[0][s], draws[1][s] when draws
+ *   [2][n_samples] is given;  t = t0 + min(floor(u1 n), n - 1), w = min(floor(u2 W), W - 1) (the
+ *   device's uniform can round to 1.0; below 0 and NaN give index 0);
+ *   x_out[p][s] = chain[t][p][w], idx_out[s] = t W + w (nullable). */
+size_t rvm_rows_quantiles_workspace_bytes(int32_t n_rows, int32_t n_q);
+int rvm_rows_quantiles(const double* x, int32_t n_rows, int64_t row_stride, int64_t n_outer, int64_t outer_stride,
+                       int64_t n_inner, const double* q, int32_t n_q, double* out, int64_t* n_valid_out,
+                       void* workspace, void* stream);
+size_t rvm_chain_cov_workspace_bytes(int32_t n_params, int32_t n_cols);
+int rvm_chain_cov(const double* chain, int32_t n_params, int32_t n_cols, int64_t t0, int64_t t1, const double* center,
+                  double* cov_out, void* workspace, void* stream);
+int rvm_chain_draw(const double* chain, int32_t n_params, int32_t n_cols, int64_t t0, int64_t t1, int32_t n_samples,
+                   uint64_t seed, uint64_t draw_id, const double* draws, double* x_out, int64_t* idx_out,
+                   void* stream);
 
 const char* rvm_last_error(void);
 int rvm_abi_version(void);

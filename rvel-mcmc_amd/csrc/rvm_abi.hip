@@ -393,6 +393,84 @@ int rvm_chain_autocov(const double* chain, const double* mean, int32_t n_params,
     return e == hipSuccess ? 0 : hip_fail(e, "rvm_chain_autocov");
 }
 
+// ---- posterior summaries (rvm_summary.hip) ----
+// (a grid's y extent: the rows; 32-bit counters: a row's elements)
+static bool quantiles_bad_shape(int32_t n_rows, int32_t n_q) {
+    return n_rows < 1 || n_rows > 65535 || n_q < 1 || n_q > RVM_MAX_QUANTILES;
+}
+
+size_t rvm_rows_quantiles_workspace_bytes(int32_t n_rows, int32_t n_q) {
+    if (quantiles_bad_shape(n_rows, n_q)) return 0;
+    return rvm::rows_quantiles_workspace_bytes(n_rows, n_q);
+}
+
+int rvm_rows_quantiles(const double* x, int32_t n_rows, int64_t row_stride, int64_t n_outer, int64_t outer_stride,
+                       int64_t n_inner, const double* q, int32_t n_q, double* out, int64_t* n_valid_out,
+                       void* workspace, void* stream) {
+    if (!x) return fail(-1, "rvm_rows_quantiles: null x");
+    if (n_rows < 1 || n_rows > 65535) return fail(-1, "rvm_rows_quantiles: n_rows must be 1 .. 65535");
+    if (row_stride < 0) return fail(-1, "rvm_rows_quantiles: row_stride must be >= 0");
+    if (n_outer < 1) return fail(-1, "rvm_rows_quantiles: n_outer must be >= 1");
+    if (outer_stride < 0) return fail(-1, "rvm_rows_quantiles: outer_stride must be >= 0");
+    if (n_inner < 1) return fail(-1, "rvm_rows_quantiles: n_inner must be >= 1");
+    if (n_outer > (int64_t)UINT32_MAX / n_inner)
+        return fail(-1, "rvm_rows_quantiles: n_outer * n_inner beyond the 2^32 - 1 elements a row's counters hold");
+    if (!q) return fail(-1, "rvm_rows_quantiles: null q");
+    if (n_q < 1 || n_q > RVM_MAX_QUANTILES) return fail(-1, "rvm_rows_quantiles: n_q must be 1 .. 16");
+    rvm::SelQ Q{};
+    Q.n_q = n_q;
+    for (int j = 0; j < n_q; j++) {
+        if (!(q[j] >= 0.0 && q[j] <= 1.0)) return fail(-1, "rvm_rows_quantiles: every q must lie in [0, 1]");
+        Q.q[j] = q[j];
+    }
+    if (!out) return fail(-1, "rvm_rows_quantiles: null out");
+    if (!workspace) return fail(-1, "rvm_rows_quantiles: null workspace");
+    if ((uintptr_t)workspace % 8 != 0) return fail(-1, "rvm_rows_quantiles: workspace must be 8-byte aligned");
+    hipError_t e = rvm::launch_rows_quantiles(x, n_rows, row_stride, n_outer, outer_stride, n_inner, Q, out, n_valid_out,
+                                              workspace, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rvm_rows_quantiles");
+}
+
+static const char* cov_bad_shape(int32_t n_params, int32_t n_cols) {
+    // (the grid: n_params^2 blocks in x, groups of 64 walkers in z)
+    if (n_params < 1 || n_params > 16384) return "n_params must be 1 .. 16384";
+    if (n_cols < 1 || n_cols > 65535 * 64) return "n_cols must be 1 .. 4194240";
+    return nullptr;
+}
+
+size_t rvm_chain_cov_workspace_bytes(int32_t n_params, int32_t n_cols) {
+    if (cov_bad_shape(n_params, n_cols)) return 0;
+    return sizeof(double) * rvm::chain_cov_workspace_doubles(n_params, n_cols);
+}
+
+int rvm_chain_cov(const double* chain, int32_t n_params, int32_t n_cols, int64_t t0, int64_t t1, const double* center,
+                  double* cov_out, void* workspace, void* stream) {
+    if (const char* m = cov_bad_shape(n_params, n_cols)) return fail(-1, std::string("rvm_chain_cov: ") + m);
+    if (!chain) return fail(-1, "rvm_chain_cov: null chain");
+    if (t0 < 0) return fail(-1, "rvm_chain_cov: t0 must be >= 0");
+    if (t1 <= t0) return fail(-1, "rvm_chain_cov: t1 must be > t0");
+    if (!center) return fail(-1, "rvm_chain_cov: null center");
+    if (!cov_out) return fail(-1, "rvm_chain_cov: null cov_out");
+    if (!workspace) return fail(-1, "rvm_chain_cov: null workspace");
+    hipError_t e = rvm::launch_chain_cov(chain, n_params, n_cols, t0, t1, center, cov_out, (double*)workspace,
+                                         (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rvm_chain_cov");
+}
+
+int rvm_chain_draw(const double* chain, int32_t n_params, int32_t n_cols, int64_t t0, int64_t t1, int32_t n_samples,
+                   uint64_t seed, uint64_t draw_id, const double* draws, double* x_out, int64_t* idx_out,
+                   void* stream) {
+    if (const char* m = chain_bad_shape(n_params, n_cols)) return fail(-1, std::string("rvm_chain_draw: ") + m);
+    if (!chain) return fail(-1, "rvm_chain_draw: null chain");
+    if (t0 < 0) return fail(-1, "rvm_chain_draw: t0 must be >= 0");
+    if (t1 <= t0) return fail(-1, "rvm_chain_draw: t1 must be > t0");
+    if (n_samples < 1) return fail(-1, "rvm_chain_draw: n_samples must be >= 1");
+    if (!x_out) return fail(-1, "rvm_chain_draw: null x_out");
+    hipError_t e = rvm::launch_chain_draw(chain, n_params, n_cols, t0, t1, n_samples, seed, draw_id, draws, x_out,
+                                          idx_out, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "rvm_chain_draw");
+}
+
 int rvm_mh_propose(int32_t n_params, int32_t n_chains, int64_t chain_begin, const double* x, const double* scales,
                    double step_size, uint64_t seed, uint64_t iteration, const double* draws, double* q_out,
                    void* stream) {

@@ -386,4 +386,10 @@ struct SmalaCache {
     int32_t* ok;
 };
 
+// rvm_rows_quantiles' q by value (rvm_summary.hip: select_narrow_kernel)
+struct SelQ {
+    int32_t n_q;  // 1..RVM_MAX_QUANTILES
+    double q[RVM_MAX_QUANTILES];
+};
+
 }  // namespace rvm

@@ -76,6 +76,15 @@ hipError_t launch_chain_moments(const double* x, int P, int W, int64_t t0, int64
 size_t chain_autocov_workspace_doubles(int P, int W, int n_lags);
 hipError_t launch_chain_autocov(const double* x, const double* mean, int P, int W, int64_t t0, int64_t t1, int lag0,
                                 int n_lags, double* acov, double* part, hipStream_t st);
+size_t rows_quantiles_workspace_bytes(int n_rows, int n_q);
+hipError_t launch_rows_quantiles(const double* x, int n_rows, int64_t row_stride, int64_t n_outer,
+                                 int64_t outer_stride, int64_t n_inner, const SelQ& Q, double* out,
+                                 int64_t* n_valid, void* workspace, hipStream_t st);
+size_t chain_cov_workspace_doubles(int P, int W);
+hipError_t launch_chain_cov(const double* x, int P, int W, int64_t t0, int64_t t1, const double* center, double* cov,
+                            double* part, hipStream_t st);
+hipError_t launch_chain_draw(const double* x, int P, int W, int64_t t0, int64_t t1, int S, uint64_t seed,
+                             uint64_t draw_id, const double* draws, double* xo, int64_t* idx, hipStream_t st);
 hipError_t launch_fd_params(int P, int n, const double* x, double rel, const double* fl, double* out, hipStream_t st);
 hipError_t launch_smala_derive(int P, int C, int E, const double* x, double rel, const double* fl,
                                const double* lp_st, const int32_t* st_st, const double* rv, const double* w,

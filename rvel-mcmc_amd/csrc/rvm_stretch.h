@@ -14,6 +14,7 @@ enum : uint32_t {
     RNG_MH_ACCEPT = 4,
     // (5 and 6: SMALA, rvm_smala.hip)
     RNG_PT_SWAP = 7,
+    RNG_CHAIN_DRAW = 8,  // (rvm_summary.hip)
 };
 
 // z = ((a - 1) u1 + 1)^2 / a  and  j = floor(u2 n1) (emcee _propose_stretch)

@@ -18,9 +18,23 @@ stops at the first window (a few tau), where the FFT computes all n lags.
     rec = ChainRecorder(sampler, capacity=8000)
     sampler.run_mcmc(8000, rec)
     d = rec.diagnostics(discard=1000)         # d.tau, d.ess, d.rhat, d.long_enough
+
+What the chain says about the posterior (driver.py:265-333 trims the host chain, draws `Ntrails` states'
+RV curves over the data and reports the parameters' distribution) is read from the same buffer
+(rvm_summary.hip), again with only the results crossing to the host:
+
+    sm = rec.summary(discard=1000)            # sm.mean, sm.sd, sm.quantiles [P][n_q], sm.cov, sm.corr
+    X, idx = rec.draw(1024, discard=1000)     # states of the chain, device tensors
+    b = rec.predict(times, n_samples=1024, discard=1000)   # b.bands [n_q][n_times]: the RV curve's band
+
+    quantiles   rvm_rows_quantiles: exact order statistics by a radix select, on the chain in place
+                and on the rows of the likelihood launch's rv_out matrix
+    cov         rvm_chain_cov around the mean of rvm_chain_moments, rvm_chain_autocov's summation order
+    draw        rvm_chain_draw: Philox keyed by (seed, sample, draw_id), with replacement
 """
 from __future__ import annotations
 
+import ctypes as C
 import dataclasses
 
 import numpy as np
@@ -97,6 +111,73 @@ class ChainDiagnostics:
     long_enough: bool
 
 
+DEFAULT_Q = (0.025, 0.16, 0.5, 0.84, 0.975)  # the median with the 68% and 95% credible intervals
+
+
+@dataclasses.dataclass
+class ChainSummary:
+    """The parameter table of the retained steps (numpy arrays).  keys: the state's get_rawkeys();
+    mean, sd [P] and quantiles [P][n_q] (of q) over all n_steps n_walkers samples; cov [P][P] around the
+    mean with the n - 1 denominator, sd its diagonal's root, corr = cov / (sd sd') with a unit diagonal."""
+    keys: list
+    q: np.ndarray
+    mean: np.ndarray
+    sd: np.ndarray
+    quantiles: np.ndarray
+    cov: np.ndarray
+    corr: np.ndarray
+    n_steps: int
+    n_walkers: int
+
+
+@dataclasses.dataclass
+class RvBands:
+    """The RV curve's credible band: bands [n_q][n_times] are the quantiles q of the model RV at `times`
+    over the samples whose evaluation succeeded, n_valid [n_times] how many those were.  With
+    return_samples also the device tensors X [P][S] (the samples), idx [S] (where in the chain they were
+    drawn; None for the caller's samples), status [S] and rv [n_times][S] as the likelihood launch wrote
+    them (columns with status != RVM_STATUS_OK are left out of the bands)."""
+    times: np.ndarray
+    q: np.ndarray
+    bands: np.ndarray
+    n_valid: np.ndarray
+    X: object = None
+    idx: object = None
+    status: object = None
+    rv: object = None
+
+
+class _Epochs:
+    """A throw-away observation set that carries only epochs (as State.get_rv builds one)."""
+
+    def __init__(self, times):
+        self.tf, self.tb = times, np.zeros(0)
+        self.rvf, self.rvb = np.zeros(len(times)), np.zeros(0)
+        self.errorf, self.errorb = np.ones(len(times)), np.zeros(0)
+        self.Npoints = 1
+
+
+def _q_array(q):
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64)).ravel()
+    if not 1 <= len(q) <= _lib.RVM_MAX_QUANTILES or not np.all((q >= 0.0) & (q <= 1.0)):
+        raise ValueError(f"q must hold 1 to {_lib.RVM_MAX_QUANTILES} values in [0, 1]")
+    return np.ascontiguousarray(q)
+
+
+def _rows_quantiles(lib, ptr, n_rows, row_stride, n_outer, outer_stride, n_inner, q, device):
+    """rvm_rows_quantiles on the current stream: (out [n_rows][n_q], n_valid [n_rows]) device tensors."""
+    torch = _torch()
+    out = torch.empty((n_rows, len(q)), dtype=torch.float64, device=device)
+    n_valid = torch.empty(n_rows, dtype=torch.int64, device=device)
+    ws = torch.empty(max(lib.rvm_rows_quantiles_workspace_bytes(n_rows, len(q)) // 8, 1), dtype=torch.int64,
+                     device=device)
+    qc = (C.c_double * len(q))(*q)
+    _lib.check(lib.rvm_rows_quantiles(ptr, n_rows, row_stride, n_outer, outer_stride, n_inner, qc, len(q),
+                                      out.data_ptr(), n_valid.data_ptr(), ws.data_ptr(), _lib.stream_handle()),
+               "rvm_rows_quantiles")
+    return out, n_valid
+
+
 class ChainRecorder:
     """Every thin-th step of `sampler` (EnsembleSampler, PTSampler, MhChains, SmalaChains), kept on the
     sampler's device.  capacity: step slots, allocated once -- push() at capacity raises ValueError; the
@@ -137,6 +218,7 @@ class ChainRecorder:
         self._mean = torch.empty((2, self.n_params, self.n_walkers), **f64)
         self._m2 = torch.empty((2, self.n_params, self.n_walkers), **f64)
         self._work = {}     # lag-block length -> (acov [P][L], workspace)
+        self._epochs = None  # predict(): (the epochs' bytes, their observation set with its cached plan)
 
     # ---- recording ---------------------------------------------------------------------------------
     def push(self):
@@ -253,6 +335,106 @@ class ChainRecorder:
         long_enough = bool(n >= 50 * np.max(tau)) and bool(np.all(window < n - 1))
         return ChainDiagnostics(tau=tau, window=window, ess=ess, rhat=rhat, mean=gmean, var=var, n_steps=n,
                                 n_walkers=W, long_enough=long_enough)
+
+    # ---- the posterior -----------------------------------------------------------------------------
+    def _range(self, discard):
+        t0, t1 = int(discard), self.n
+        if t0 < 0 or t0 >= t1:
+            raise ValueError(f"discard must leave at least one of the {self.n} recorded steps")
+        return t0, t1
+
+    def summary(self, discard=0, q=DEFAULT_Q):
+        """ChainSummary of the recorded steps [discard, n): per parameter the mean, the standard deviation
+        and the quantiles q (rvm_rows_quantiles over the chain in place), and the parameters' covariance
+        around the mean (rvm_chain_cov) with its correlation matrix.  Synchronises: only the [P], [P][n_q]
+        and [P][P] results cross to the host."""
+        torch = _torch()
+        t0, t1 = self._range(discard)
+        n, W, P = t1 - t0, self.n_walkers, self.n_params
+        q = _q_array(q)
+        with torch.cuda.device(self.device):
+            mean, _ = self._moments(t0, t1, 0)
+            center = mean.mean(1).contiguous()  # (diagnostics()'s mean, the same operations)
+            quant, _ = _rows_quantiles(self.lib, self._chain.data_ptr() + 8 * t0 * P * W, P, W, n, P * W, W, q,
+                                       self.device)
+            cov = torch.empty((P, P), dtype=torch.float64, device=self.device)
+            ws = torch.empty(max(self.lib.rvm_chain_cov_workspace_bytes(P, W) // 8, 1), dtype=torch.float64,
+                             device=self.device)
+            _lib.check(self.lib.rvm_chain_cov(self._chain.data_ptr(), P, W, t0, t1, center.data_ptr(), cov.data_ptr(),
+                                              ws.data_ptr(), _lib.stream_handle()), "rvm_chain_cov")
+            center, quant, cov = center.cpu().numpy(), quant.cpu().numpy(), cov.cpu().numpy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            sd = np.sqrt(np.diag(cov))
+            corr = cov / (sd[:, None] * sd[None, :])
+        corr[np.diag_indices(P)] = np.where(sd > 0, 1.0, np.nan)
+        state = getattr(self.sampler, "state", None)
+        keys = list(state.get_rawkeys()) if state is not None else [str(p) for p in range(P)]
+        return ChainSummary(keys=keys, q=q, mean=center, sd=sd, quantiles=quant, cov=cov, corr=corr, n_steps=n,
+                            n_walkers=W)
+
+    def draw(self, n_samples, discard=0, seed=0, draw_id=0):
+        """(X [P][S], idx [S]) device tensors: n_samples states of the recorded steps [discard, n), uniform
+        with replacement (rvm_chain_draw; Philox keyed by seed, sample and draw_id, so a call repeats);
+        idx = step * n_walkers + walker into chain().  Launches only."""
+        torch = _torch()
+        t0, t1 = self._range(discard)
+        S = int(n_samples)
+        if S < 1:
+            raise ValueError("n_samples must be at least 1")
+        X = torch.empty((self.n_params, S), dtype=torch.float64, device=self.device)
+        idx = torch.empty(S, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rvm_chain_draw(self._chain.data_ptr(), self.n_params, self.n_walkers, t0, t1, S,
+                                               int(seed), int(draw_id), 0, X.data_ptr(), idx.data_ptr(),
+                                               _lib.stream_handle()), "rvm_chain_draw")
+        return X, idx
+
+    def predict(self, times, n_samples=1024, discard=0, q=DEFAULT_Q, seed=0, samples=None, return_samples=False):
+        """RvBands: the quantiles q of the model RV at `times` over n_samples states drawn from the recorded
+        steps [discard, n) (or over the caller's samples [P][S], a device tensor of free-parameter vectors)
+        -- the credible band the reference draws as `Ntrails` ghost curves (driver.py:265-333).  One
+        likelihood launch with rv_out on a plan built on `times` (as State.get_rv: the sampler's state,
+        parameter map and Hill factor; for PTSampler the cold temperature, which is what is recorded), the
+        columns of samples that are not RVM_STATUS_OK masked to NaN, then rvm_rows_quantiles over the
+        epochs' rows; n_valid counts the samples behind each epoch.  At most RVM_MAX_EPOCHS_PER_DIRECTION
+        epochs with t >= 0 and as many with t < 0 (ValueError beyond).  Synchronises for the [n_q][n_times]
+        result."""
+        torch = _torch()
+        times = np.ascontiguousarray(np.asarray(times, dtype=np.float64).ravel())
+        if len(times) < 1 or not np.all(np.isfinite(times)):
+            raise ValueError("times must be a non-empty array of finite epochs")
+        cap = _lib.RVM_MAX_EPOCHS_PER_DIRECTION
+        if int((times >= 0).sum()) > cap or int((times < 0).sum()) > cap:
+            raise ValueError(f"at most {cap} epochs with t >= 0 and {cap} with t < 0 per call "
+                             f"(RVM_MAX_EPOCHS_PER_DIRECTION)")
+        q = _q_array(q)
+        sampler = self.sampler
+        state = getattr(sampler, "state", None)
+        if state is None or not hasattr(sampler, "pmap"):
+            raise TypeError(f"{type(sampler).__name__} has no state / pmap: nothing to evaluate the RV with")
+        idx = None
+        if samples is None:
+            X, idx = self.draw(n_samples, discard, seed)
+        else:
+            X = samples
+            if (not torch.is_tensor(X) or X.dtype != torch.float64 or X.dim() != 2 or X.shape[0] != self.n_params
+                    or X.shape[1] < 1 or X.device != self._chain.device):
+                raise ValueError("samples must be a float64 tensor [n_params][S] on the recorder's device")
+            X = X.contiguous()
+        key = times.tobytes()
+        if self._epochs is None or self._epochs[0] != key:
+            self._epochs = (key, _Epochs(times))  # (keeps the plan plan_for caches on it)
+        hf = getattr(sampler, "hill_factor", state.hillRadiusFactor)
+        with torch.cuda.device(self.device):
+            _, status, rv = state.get_logp_batch(self._epochs[1], X, hill_factor=hf, want_rv=True, pmap=sampler.pmap)
+            masked = torch.where((status == _lib.RVM_STATUS_OK)[None, :], rv, torch.full_like(rv, float("nan")))
+            S = int(X.shape[1])
+            bands, n_valid = _rows_quantiles(self.lib, masked.data_ptr(), len(times), S, 1, S, S, q, self.device)
+            bands, n_valid = bands.cpu().numpy(), n_valid.cpu().numpy()
+        out = RvBands(times=times, q=q, bands=np.ascontiguousarray(bands.T), n_valid=n_valid)
+        if return_samples:
+            out.X, out.idx, out.status, out.rv = X, idx, status, rv
+        return out
 
 
 def run_mcmc(sampler, n_steps, recorder=None):
