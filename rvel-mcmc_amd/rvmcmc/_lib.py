@@ -185,6 +185,18 @@ def check(rc: int, what: str):
         raise RvmError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
 
 
+def _torch():
+    """torch, imported at first use (the package's one accessor: the ABI loads without it)."""
+    import torch
+
+    return torch
+
+
+def ptr(t) -> int:
+    """Device address of a tensor for the C ABI; None -> 0 (a nullable argument left out)."""
+    return t.data_ptr() if t is not None else 0
+
+
 def stream_handle(stream=None) -> int:
     """hipStream_t of a torch stream (default: the current stream of the current device)."""
     import torch

@@ -40,13 +40,8 @@ import dataclasses
 import numpy as np
 
 from . import _lib
-
-
-def _torch():
-    import torch
-
-    return torch
-
+from ._lib import _torch, ptr
+from .observations import Epochs
 
 LAG_BLOCK0 = 64  # the first two lag blocks of the window search: [0, 64), [64, 128), then doubling
 
@@ -147,16 +142,6 @@ class RvBands:
     rv: object = None
 
 
-class _Epochs:
-    """A throw-away observation set that carries only epochs (as State.get_rv builds one)."""
-
-    def __init__(self, times):
-        self.tf, self.tb = times, np.zeros(0)
-        self.rvf, self.rvb = np.zeros(len(times)), np.zeros(0)
-        self.errorf, self.errorb = np.ones(len(times)), np.zeros(0)
-        self.Npoints = 1
-
-
 def _q_array(q):
     q = np.atleast_1d(np.asarray(q, dtype=np.float64)).ravel()
     if not 1 <= len(q) <= _lib.RVM_MAX_QUANTILES or not np.all((q >= 0.0) & (q <= 1.0)):
@@ -244,8 +229,7 @@ class ChainRecorder:
                 ld = x.stride(0) if x.shape[0] > 1 else x.shape[1]  # (a single row's stride means nothing)
                 _lib.check(self.lib.rvm_chain_record(self.n_params, cnt, x.data_ptr(), ld, s.get("col0", 0),
                                                      self.walker_stride, slot.data_ptr(), self.n_walkers, col,
-                                                     lnp.data_ptr() if lslot is not None else 0,
-                                                     lslot.data_ptr() if lslot is not None else 0, sh),
+                                                     ptr(lnp if lslot is not None else None), ptr(lslot), sh),
                            "rvm_chain_record")
                 col += cnt
         self.n += 1
@@ -423,7 +407,7 @@ class ChainRecorder:
             X = X.contiguous()
         key = times.tobytes()
         if self._epochs is None or self._epochs[0] != key:
-            self._epochs = (key, _Epochs(times))  # (keeps the plan plan_for caches on it)
+            self._epochs = (key, Epochs(times))  # (keeps the plan plan_for caches on it)
         hf = getattr(sampler, "hill_factor", state.hillRadiusFactor)
         with torch.cuda.device(self.device):
             _, status, rv = state.get_logp_batch(self._epochs[1], X, hill_factor=hf, want_rv=True, pmap=sampler.pmap)

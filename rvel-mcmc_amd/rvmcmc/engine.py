@@ -16,6 +16,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
+from ._lib import _torch, ptr
 
 KERNEL_KEYS = ("m", "a", "h", "k", "l")
 KERNEL_KEYS_INCLINED = KERNEL_KEYS + ("ix", "iy")
@@ -148,14 +149,11 @@ def min_period(planets) -> float:
     return best
 
 
-def _torch():
-    import torch
-
-    return torch
-
-
-def default_device():
+def default_device(device=None):
+    """`device` as a torch.device; None: the current HIP device."""
     torch = _torch()
+    if device is not None:
+        return torch.device(device)
     if not torch.cuda.is_available():
         raise _lib.RvmError("no HIP device visible: the likelihood runs only on the GPU (no CPU fallback)")
     return torch.device("cuda", torch.cuda.current_device())
@@ -168,7 +166,7 @@ class LoglPlan:
                  period_hint=0.0, inclined=False, resolve=(0.0, 0)):
         torch = _torch()
         self.lib = _lib.load()
-        self.device = torch.device(device) if device is not None else default_device()
+        self.device = default_device(device)
         t = np.ascontiguousarray(np.asarray(t, dtype=np.float64))
         rv = np.ascontiguousarray(np.asarray(rv, dtype=np.float64))
         sigma = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64))
@@ -222,33 +220,32 @@ class LoglPlan:
                 tot[k] += v
         return f
 
+    def _words(self, fn, names, reset, stream) -> dict:
+        """One of the rvm_plan_hedge_* read-outs: len(names) int64 words behind (plan, reset) and
+        before the stream, as a dict."""
+        vals = [C.c_int64() for _ in names]
+        _lib.check(getattr(self.lib, fn)(self._h, int(bool(reset)), *[C.byref(v) for v in vals],
+                                         _lib.stream_handle(stream)), fn)
+        return {k: v.value for k, v in zip(names, vals)}
+
     def hedge_stats(self, reset=False, stream=None) -> dict:
         """rvm_plan_hedge_stats (synchronises the stream): walker slots whose second halving pass ran
         beside the likelihood kernel, pass-2 walker-directions the refinement kernel replayed from
         those, and pass-2 walker-directions of such launches it integrated itself.  Timing-dependent,
         hence not part of faults()."""
-        h, r, m = C.c_int64(), C.c_int64(), C.c_int64()
-        _lib.check(self.lib.rvm_plan_hedge_stats(self._h, int(bool(reset)), C.byref(h), C.byref(r), C.byref(m),
-                                                 _lib.stream_handle(stream)), "rvm_plan_hedge_stats")
-        return dict(hedged=h.value, replayed=r.value, missed=m.value)
+        return self._words("rvm_plan_hedge_stats", ("hedged", "replayed", "missed"), reset, stream)
 
     def hedge_marks(self, reset=False, stream=None) -> dict:
         """rvm_plan_hedge_marks (synchronises the stream): hedge (group, direction) marks the refinement kernel
         wrote because no listed walker slot could use the block, and hedge blocks that stopped on theirs.
         Timing-dependent, as hedge_stats()."""
-        m, g = C.c_int64(), C.c_int64()
-        _lib.check(self.lib.rvm_plan_hedge_marks(self._h, int(bool(reset)), C.byref(m), C.byref(g),
-                                                 _lib.stream_handle(stream)), "rvm_plan_hedge_marks")
-        return dict(marked=m.value, gave_up=g.value)
+        return self._words("rvm_plan_hedge_marks", ("marked", "gave_up"), reset, stream)
 
     def hedge_waits(self, reset=False, stream=None) -> dict:
         """rvm_plan_hedge_waits (synchronises the stream): trials of team A that polled for a running hedge
         block, polls that ended with the group finished from the hedge, and polls after which pass 2 was
         handed on to team B (waited = late_hits + gave_way).  Timing-dependent, as hedge_stats()."""
-        w, h, g = C.c_int64(), C.c_int64(), C.c_int64()
-        _lib.check(self.lib.rvm_plan_hedge_waits(self._h, int(bool(reset)), C.byref(w), C.byref(h), C.byref(g),
-                                                 _lib.stream_handle(stream)), "rvm_plan_hedge_waits")
-        return dict(waited=w.value, late_hits=h.value, gave_way=g.value)
+        return self._words("rvm_plan_hedge_waits", ("waited", "late_hits", "gave_way"), reset, stream)
 
     def check_faults(self, what="plan", stream=None, group=None) -> dict:
         """Raise RvmError on hand-off timeouts, NONFINITE results, or (a plan that refines, resolve_max
@@ -297,18 +294,29 @@ class LoglPlan:
         return dict(steps_fwd=vals[0].value, steps_bwd=vals[1].value, epochs_fwd=vals[2].value,
                     epochs_bwd=vals[3].value)
 
+    def _need_f64(self, tensors, msg, contiguous=True, dim=None):
+        """Every tensor float64 on the plan's device (contiguous; dim-dimensional), or ValueError(msg)."""
+        f64 = _torch().float64
+        for t in tensors:
+            if (t.dtype != f64 or t.device != self.device or (contiguous and not t.is_contiguous())
+                    or (dim is not None and t.dim() != dim)):
+                raise ValueError(msg)
+
+    def _kernel_params(self, params, name_rows=False):
+        """logl's / derivs' parameter block [rows][W], checked and contiguous."""
+        self._need_f64((params,), "params must be a 2-D float64 tensor on the plan's device", False, 2)
+        if params.shape[0] != self.rows:
+            rows = f" (m,a,h,k,l{',ix,iy' if self.inclined else ''} per planet)" if name_rows else ""
+            raise ValueError(f"params must have {self.rows} rows{rows}")
+        return params.contiguous()
+
     def logl(self, params, hill_factor=1.0, want_rv=False, out=None, status=None, rv_out=None, stream=None):
         """params: float64 device tensor [5*n_planets][W] ([7*n_planets][W] for an inclined plan) ->
         (logl[W], status[W], rv|None).
 
         rv (if requested) is [n_obs][W], rows in the plan's input epoch order."""
         torch = _torch()
-        if params.dtype != torch.float64 or params.device != self.device or params.dim() != 2:
-            raise ValueError("params must be a 2-D float64 tensor on the plan's device")
-        if params.shape[0] != self.rows:
-            raise ValueError(f"params must have {self.rows} rows (m,a,h,k,l{',ix,iy' if self.inclined else ''} "
-                             f"per planet)")
-        params = params.contiguous()
+        params = self._kernel_params(params, name_rows=True)
         W = params.shape[1]
         if W > self.max_walkers:
             raise ValueError(f"{W} walkers exceed the plan's max_walkers={self.max_walkers}")
@@ -333,11 +341,7 @@ class LoglPlan:
         free parameters (ParamMap.slots).  Returns (logl[C], grad[P][C], hess[P][P][C], status[C]);
         gradient and Hessian are NaN where status != 0."""
         torch = _torch()
-        if params.dtype != torch.float64 or params.device != self.device or params.dim() != 2:
-            raise ValueError("params must be a 2-D float64 tensor on the plan's device")
-        if params.shape[0] != self.rows:
-            raise ValueError(f"params must have {self.rows} rows")
-        params = params.contiguous()
+        params = self._kernel_params(params)
         C_ = params.shape[1]
         rows = np.ascontiguousarray(np.asarray(dir_rows, dtype=np.int32))
         P = len(rows)
@@ -361,10 +365,8 @@ class LoglPlan:
         c_aos [n1][dim] (walker-major), walker logL of the proposals, accept -- one launch.  X0
         [dim][n0] and lnp0 [n0] are updated in place, and X0_aos [n0][dim] (optional, the
         walker-major mirror of X0) too; lnp_new / status (optional) receive the proposals' logl."""
-        torch = _torch()
-        for t in (X0, lnp0, c_aos) + ((X0_aos,) if X0_aos is not None else ()):
-            if t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous():
-                raise ValueError("X0, lnp0, c_aos, X0_aos must be contiguous float64 tensors on the plan's device")
+        self._need_f64((X0, lnp0, c_aos) + ((X0_aos,) if X0_aos is not None else ()),
+                       "X0, lnp0, c_aos, X0_aos must be contiguous float64 tensors on the plan's device")
         dim, n0 = X0.shape
         if c_aos.dim() != 2 or c_aos.shape[1] != dim or lnp0.shape != (n0,):
             raise ValueError("shape mismatch between X0 [dim][n0], lnp0 [n0] and c_aos [n1][dim]")
@@ -372,13 +374,11 @@ class LoglPlan:
             raise ValueError("X0_aos must be [n0][dim]")
         if n0 > self.max_walkers:
             raise ValueError(f"{n0} walkers exceed the plan's max_walkers={self.max_walkers}")
-        with torch.cuda.device(self.device):
+        with _torch().cuda.device(self.device):
             rc = self.lib.rvm_stretch_half_step(
-                self._h, C.byref(pmap.c_map()), dim, n0, int(s0_begin), X0.data_ptr(),
-                X0_aos.data_ptr() if X0_aos is not None else 0, lnp0.data_ptr(), c_aos.shape[0], c_aos.data_ptr(),
-                float(a), int(seed), int(iteration), int(half), float(hill_factor),
-                lnp_new.data_ptr() if lnp_new is not None else 0, status.data_ptr() if status is not None else 0,
-                accepted.data_ptr() if accepted is not None else 0, _lib.stream_handle(stream))
+                self._h, C.byref(pmap.c_map()), dim, n0, int(s0_begin), X0.data_ptr(), ptr(X0_aos), lnp0.data_ptr(),
+                c_aos.shape[0], c_aos.data_ptr(), float(a), int(seed), int(iteration), int(half), float(hill_factor),
+                ptr(lnp_new), ptr(status), ptr(accepted), _lib.stream_handle(stream))
         _lib.check(rc, "rvm_stretch_half_step")
 
     def stretch_iteration_begin(self, pmap, X0, lnp0, X1, c0_aos, c1_aos, s0_begin, s1_begin, a, seed, iteration,
@@ -390,10 +390,8 @@ class LoglPlan:
         [n_half][dim] as at the start of the iteration (unchanged until the end call).  lnp1 [n]
         (optional): half 1's log-probabilities, the accept inputs of its slots."""
         torch = _torch()
-        for t in (X0, lnp0, X1, c0_aos, c1_aos, lnp_spec):
-            if t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous():
-                raise ValueError("X0, lnp0, X1, c0_aos, c1_aos, lnp_spec must be contiguous float64 tensors on the "
-                                 "plan's device")
+        self._need_f64((X0, lnp0, X1, c0_aos, c1_aos, lnp_spec), "X0, lnp0, X1, c0_aos, c1_aos, lnp_spec must be "
+                       "contiguous float64 tensors on the plan's device")
         dim, n = X0.shape
         n_half = c0_aos.shape[0]
         if X1.shape != (dim, n) or lnp0.shape != (n,) or c0_aos.shape != (n_half, dim) or c1_aos.shape != (n_half, dim):
@@ -410,10 +408,9 @@ class LoglPlan:
         with torch.cuda.device(self.device):
             rc = self.lib.rvm_stretch_iteration_begin(
                 self._h, C.byref(pmap.c_map()), dim, n, int(s0_begin), int(s1_begin), X0.data_ptr(), lnp0.data_ptr(),
-                X1.data_ptr(), lnp1.data_ptr() if lnp1 is not None else 0, n_half, c0_aos.data_ptr(), c1_aos.data_ptr(),
-                float(a), int(seed), int(iteration),
-                float(hill_factor), lnp_spec.data_ptr(), status_spec.data_ptr(), dec.data_ptr(),
-                accepted0.data_ptr() if accepted0 is not None else 0, _lib.stream_handle(stream))
+                X1.data_ptr(), ptr(lnp1), n_half, c0_aos.data_ptr(), c1_aos.data_ptr(), float(a), int(seed),
+                int(iteration), float(hill_factor), lnp_spec.data_ptr(), status_spec.data_ptr(), dec.data_ptr(),
+                ptr(accepted0), _lib.stream_handle(stream))
         _lib.check(rc, "rvm_stretch_iteration_begin")
 
     def close(self):
@@ -443,7 +440,6 @@ def stretch_iteration_end(X0, X0_aos, dec, dec_all, X1, X1_aos, lnp1, c0_aos, c1
     for t in (X0_aos, X1_aos):
         if t is not None and t.shape != (n, dim):
             raise ValueError("mirrors must be [n][dim]")
-    ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
     with torch.cuda.device(X1.device):
         rc = lib.rvm_stretch_iteration_end(dim, n, int(s0_begin), int(s1_begin), X0.data_ptr(), ptr(X0_aos),
                                            dec.data_ptr(), dec_all.data_ptr(), X1.data_ptr(), ptr(X1_aos),
@@ -465,14 +461,37 @@ def obs_arrays(obs):
 FAULT_CHECK_EVERY = 256  # sampler iterations between automatic rvm_plan_faults checks (0: never)
 
 
-def periodic_fault_check(sampler, plan):
-    """Every `fault_check_every` iterations (a sampler attribute, default FAULT_CHECK_EVERY) read the
-    plan's counters and raise on a hand-off timeout or a NONFINITE result (LoglPlan.check_faults):
-    the check synchronises the stream, so it is amortised over many iterations rather than run per
-    step; `sampler.check_faults()` runs it on demand."""
+def periodic_fault_check(sampler):
+    """Every `fault_check_every` iterations (a sampler attribute, default FAULT_CHECK_EVERY) run
+    `sampler.check_faults()`: read its plans' counters and raise on a hand-off timeout or a NONFINITE
+    result (LoglPlan.check_faults).  The check synchronises the stream, so it is amortised over many
+    iterations rather than run per step.  A sampler whose `plan` is None (an EnsembleSampler over
+    host ops) has nothing to read and is skipped; SmalaChains has two plans and no `plan`."""
     every = getattr(sampler, "fault_check_every", FAULT_CHECK_EVERY)
-    if plan is not None and every and sampler.iteration % every == 0:
-        sampler.last_faults = plan.check_faults(type(sampler).__name__, group=fault_group(sampler))
+    if every and sampler.iteration % every == 0 and getattr(sampler, "plan", sampler) is not None:
+        sampler.check_faults()
+
+
+class DeviceSampler:
+    """What EnsembleSampler, PTSampler, MhChains and SmalaChains share around their step()."""
+
+    def _end_step(self):
+        """The end of every step(): count the iteration; the periodic fault check."""
+        self.iteration += 1
+        periodic_fault_check(self)
+
+    def run_mcmc(self, n_steps, recorder=None):
+        """n_steps of step(); every recorder.thin-th one goes into `recorder` (chain.ChainRecorder)."""
+        from .chain import run_mcmc
+
+        return run_mcmc(self, n_steps, recorder)
+
+    def check_faults(self):
+        """Raise on level-split hand-off timeouts, NONFINITE or UNRESOLVED log-likelihoods since the
+        last check (rvm_plan_faults; also run every FAULT_CHECK_EVERY iterations by step());
+        returns the counters, including the walker-directions the adaptive resolution refined."""
+        self.last_faults = self.plan.check_faults(type(self).__name__, group=fault_group(self))
+        return self.last_faults
 
 
 def fault_group(sampler):
@@ -501,7 +520,7 @@ def plan_for(obs, n_planets, dt, levels, max_walkers, device=None, period_hint=0
     """Cached LoglPlan on an Observation object (keyed by device, the caller's current stream and
     the integrator settings: a plan's workspace is single-stream, include/rvmcmc.h)."""
     torch = _torch()
-    dev = torch.device(device) if device is not None else default_device()
+    dev = default_device(device)
     cache = obs.__dict__.setdefault("_rvm_plans", {})
     mult = level_multipliers(levels)
     stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
@@ -520,6 +539,18 @@ def plan_for(obs, n_planets, dt, levels, max_walkers, device=None, period_hint=0
     return plan
 
 
+def plan_for_state(state, obs, max_walkers, device=None, adaptive=True) -> LoglPlan:
+    """plan_for with everything a State decides: its planets' count and inclination, its integrator's
+    step, levels, hint and resolve tuple.  The one place that spells a State's cache key, so two
+    look-ups for one state, device and stream return the same plan (SmalaChains.check_faults reads
+    the counters of the plans its launches ran on this way).  adaptive=False: the same step with
+    the adaptive resolution off, resolve (0.0, 0) -- SMALA's stencil plan."""
+    it, planets = state.integrator, state.planets
+    dt, mult, hint = it.plan_args(planets)
+    return plan_for(obs, len(planets), dt, mult, max_walkers, device, hint, is_inclined(planets),
+                    it.resolve(planets) if adaptive else (0.0, 0))
+
+
 class ParamMap:
     """Free-parameter vectors of a State  <->  kernel SoA parameter blocks.
 
@@ -533,7 +564,7 @@ class ParamMap:
         self.n_planets = len(state.planets)
         if not 1 <= self.n_planets <= _lib.RVM_MAX_PLANETS:
             raise ValueError(f"1..{_lib.RVM_MAX_PLANETS} planets supported, got {self.n_planets}")
-        self.inclined = any(("ix" in p) or ("iy" in p) for p in state.planets)
+        self.inclined = is_inclined(state.planets)
         keys = KERNEL_KEYS_INCLINED if self.inclined else KERNEL_KEYS
         R = len(keys)
         self.rows_per_planet = R

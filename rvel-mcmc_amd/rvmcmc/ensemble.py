@@ -27,13 +27,16 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _lib, chain, engine
+from . import _lib, engine
+from ._lib import _torch, ptr
 
 
-def _torch():
-    import torch
-
-    return torch
+def check_walker_count(nwalkers, dim):
+    """emcee's two conditions on an ensemble's size (EnsembleSampler and PTSampler)."""
+    if nwalkers % 2 != 0:
+        raise ValueError("The number of walkers must be even.")
+    if nwalkers < 2 * dim:
+        raise ValueError("The number of walkers needs to be more than twice the dimension of your parameter space.")
 
 
 class DeviceOps:
@@ -42,56 +45,61 @@ class DeviceOps:
     numpy restatements of these three to exercise the sharding logic on CPU with gloo.)"""
 
     def __init__(self, sampler):
-        torch = _torch()
         self.s = sampler
         self.lib = _lib.load()
-        st = sampler.state
-        dt, mult, hint = st.integrator.plan_args(st.planets)
         # room for the 3 n walker slots of a speculative iteration (iteration_begin)
-        self.plan = engine.plan_for(sampler.obs, sampler.pmap.n_planets, dt, mult, 3 * sampler.nloc,
-                                    sampler.device, hint, sampler.pmap.inclined, st.integrator.resolve(st.planets))
+        self.plan = engine.plan_for_state(sampler.state, sampler.obs, 3 * sampler.nloc, sampler.device)
         self.timing = None  # set to [] to collect (start_event, end_event, n_walkers) per logL launch
         self.track_status = False  # set True to histogram per-walker statuses (costs a small kernel)
-        self.status_counts = torch.zeros(4, dtype=torch.int64, device=sampler.device)
+        self.status_counts = _torch().zeros(4, dtype=_torch().int64, device=sampler.device)
+
+    # The launches below test `timing` and `track_status` themselves and call these only when they are
+    # set: with both off (the benchmark) a launch pays the two tests and no call.
+    def _timing_start(self):
+        """A HIP event recorded on the launch stream, before a likelihood launch."""
+        e0 = _torch().cuda.Event(enable_timing=True)
+        e0.record()
+        return e0
+
+    def _timing_stop(self, e0, n_walkers):
+        """The event after the launch; (start_event, end_event, n_walkers) goes into `timing`."""
+        e1 = _torch().cuda.Event(enable_timing=True)
+        e1.record()
+        self.timing.append((e0, e1, n_walkers))
+
+    def _count_status(self, st):
+        torch = _torch()
+        self.status_counts.index_add_(0, st.long(), torch.ones_like(st, dtype=torch.int64))
 
     def propose(self, X0, c, half, q, z, draws=None):
         s = self.s
         _lib.check(self.lib.rvm_stretch_propose(s.dim, s.nloc, s.global_begin(half), X0.data_ptr(), s.halfk,
-                                                c.data_ptr(), s.a, s.seed, s.iteration, half,
-                                                draws.data_ptr() if draws is not None else 0, q.data_ptr(),
+                                                c.data_ptr(), s.a, s.seed, s.iteration, half, ptr(draws), q.data_ptr(),
                                                 z.data_ptr(), _lib.stream_handle()), "rvm_stretch_propose")
 
     def logl(self, X, out=None, status=None):
-        torch = _torch()
         K = self.s.pmap.to_kernel(X)
-        if self.timing is not None:  # HIP events on the launch stream, around the likelihood launch only
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        e0 = self._timing_start() if self.timing is not None else None  # (around the likelihood launch only)
         lp, st, _ = self.plan.logl(K, hill_factor=self.s.hill_factor, out=out, status=status)
-        if self.timing is not None:
-            e1.record()
-            self.timing.append((e0, e1, X.shape[1]))
+        if e0 is not None:
+            self._timing_stop(e0, X.shape[1])
         if self.track_status:
-            self.status_counts.index_add_(0, st.long(), torch.ones_like(st, dtype=torch.int64))
+            self._count_status(st)
         return lp, st
 
     def fused_half_step(self, X0, X0_aos, lnp0, c_aos, half, lnp_new, status, accepted):
         """propose + logl + accept in one likelihood launch (rvm_stretch_half_step), bit-identical
         to the three-launch sequence with Philox draws.  c_aos: the complement walker-major
         [n1][dim]; X0_aos: this half's walker-major mirror (updated on accept with X0)."""
-        torch = _torch()
         s = self.s
-        if self.timing is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        e0 = self._timing_start() if self.timing is not None else None
         self.plan.stretch_half_step(s.pmap, X0, lnp0, c_aos, s.global_begin(half), s.a, s.seed, s.iteration,
                                     half, s.hill_factor, lnp_new=lnp_new, status=status, accepted=accepted,
                                     X0_aos=X0_aos)
-        if self.timing is not None:
-            e1.record()
-            self.timing.append((e0, e1, X0.shape[1]))
+        if e0 is not None:
+            self._timing_stop(e0, X0.shape[1])
         if self.track_status:
-            self.status_counts.index_add_(0, status.long(), torch.ones_like(status, dtype=torch.int64))
+            self._count_status(status)
 
     def speculation_pays(self):
         """Whether one launch of 3 n walker slots (a whole speculative iteration) beats two
@@ -124,50 +132,41 @@ class DeviceOps:
 
     def iteration_begin(self, c0, c1):
         """rvm_stretch_iteration_begin on the sampler's buffers (half 0 updated, all 3 n logl)."""
-        torch = _torch()
         s = self.s
         n = s.nloc
-        if self.timing is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        e0 = self._timing_start() if self.timing is not None else None
         self.plan.stretch_iteration_begin(s.pmap, s.pos[0], s.lnp[0], s.pos[1], c0, c1, s.global_begin(0),
                                           s.global_begin(1), s.a, s.seed, s.iteration, s._lnp_spec, s._st_spec,
                                           s._dec, hill_factor=s.hill_factor, accepted0=s.naccepted[:n], lnp1=s.lnp[1])
-        if self.timing is not None:
-            e1.record()
-            self.timing.append((e0, e1, 3 * n))
+        if e0 is not None:
+            self._timing_stop(e0, 3 * n)
         if self.track_status:
-            st = s._st_spec[:n]
-            self.status_counts.index_add_(0, st.long(), torch.ones_like(st, dtype=torch.int64))
+            self._count_status(s._st_spec[:n])
 
     def iteration_end(self, c0, c1, dec_all):
         """rvm_stretch_iteration_end: half 1's accepts, both walker-major mirrors refreshed."""
-        torch = _torch()
         s = self.s
         n = s.nloc
         engine.stretch_iteration_end(s.pos[0], s.pos_aos[0], s._dec, dec_all, s.pos[1], s.pos_aos[1], s.lnp[1], c0, c1,
                                      s._lnp_spec, s._st_spec, s.global_begin(0), s.global_begin(1), s.a, s.seed,
                                      s.iteration, accepted1=s.naccepted[n:], lnp_new=s._lnp_new, status_new=s._status)
         if self.track_status:
-            self.status_counts.index_add_(0, s._status.long(), torch.ones_like(s._status, dtype=torch.int64))
+            self._count_status(s._status)
 
     def accept(self, X0, lnp0, q, lnp_new, z, half, accepted, draws=None):
         s = self.s
         _lib.check(self.lib.rvm_stretch_accept(s.dim, s.nloc, s.global_begin(half), X0.data_ptr(), lnp0.data_ptr(),
                                                q.data_ptr(), lnp_new.data_ptr(), z.data_ptr(), s.seed, s.iteration,
-                                               half, draws.data_ptr() if draws is not None else 0,
-                                               accepted.data_ptr(), _lib.stream_handle()), "rvm_stretch_accept")
+                                               half, ptr(draws), accepted.data_ptr(), _lib.stream_handle()),
+                   "rvm_stretch_accept")
 
 
-class EnsembleSampler:
+class EnsembleSampler(engine.DeviceSampler):
     def __init__(self, nwalkers, state, obs, a=2.0, seed=0, device=None, hill_factor=None, group=None,
                  pmap=None, ops=None):
         torch = _torch()
         dim = state.Nvars
-        if nwalkers % 2 != 0:
-            raise ValueError("The number of walkers must be even.")
-        if nwalkers < 2 * dim:
-            raise ValueError("The number of walkers needs to be more than twice the dimension of your parameter space.")
+        check_walker_count(nwalkers, dim)
         self.k = int(nwalkers)
         self.dim = dim
         self.comm_timing = None  # set to [] to collect HIP events around the collectives (N > 1)
@@ -177,7 +176,7 @@ class EnsembleSampler:
         self.obs = obs
         self.pmap = pmap or state.param_map()
         self.hill_factor = state.hillRadiusFactor if hill_factor is None else float(hill_factor)
-        self.device = torch.device(device) if device is not None else engine.default_device()
+        self.device = engine.default_device(device)
         # distributed layout: rank r owns walkers [r*nloc, (r+1)*nloc) of each half
         self.group = group
         if group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
@@ -336,25 +335,13 @@ class EnsembleSampler:
             A, B = self.pos
             self.half_step(A, self.lnp[0], B, 0)
             self.half_step(B, self.lnp[1], A, 1)
-        self.iteration += 1
-        engine.periodic_fault_check(self, self.plan)
+        self._end_step()
 
     def _chain_segments(self):
         """Where this rank's walkers live, for chain.ChainRecorder: half 0, then half 1."""
         if getattr(self, "pos", None) is None:
             raise ValueError("set_positions first")
         return [dict(x=self.pos[h], lnp=self.lnp[h], col0=0, n=self.nloc) for h in (0, 1)]
-
-    def run_mcmc(self, n_steps, recorder=None):
-        """n_steps iterations; every recorder.thin-th one goes into `recorder` (chain.ChainRecorder)."""
-        return chain.run_mcmc(self, n_steps, recorder)
-
-    def check_faults(self):
-        """Raise on level-split hand-off timeouts or NONFINITE log-likelihoods since the last check
-        (rvm_plan_faults; also run every FAULT_CHECK_EVERY iterations by step()); returns the
-        counters, including walker-directions refined by the adaptive resolution."""
-        self.last_faults = self.plan.check_faults(type(self).__name__, group=engine.fault_group(self))
-        return self.last_faults
 
     def gather_mirrors(self):
         """Both halves' walker-major mirrors [W/2][dim] in global order: this rank's own at N = 1,
@@ -398,42 +385,30 @@ class EnsembleSampler:
         self.nevals += 2 * self.nloc
         self.nevals_speculative += self.nloc
 
+    def _gather_halves(self, halves):
+        """This rank's slices of the two halves, each [nloc] (+ trailing axes) -> all walkers [W] (+
+        trailing axes) in global order on every rank (host numpy): one all-gather per half."""
+        torch = _torch()
+        if self.world > 1:
+            local, halves = halves, []
+            for x in local:
+                buf = torch.empty((self.world * self.nloc,) + tuple(x.shape[1:]), dtype=x.dtype, device=self.device)
+                torch.distributed.all_gather_into_tensor(buf, x.contiguous(), group=self.group)
+                halves.append(buf)
+        return torch.cat(halves, 0).cpu().numpy()
+
     def gather_positions(self):
         """All walkers [W][dim] on every rank (host numpy), global order."""
-        torch = _torch()
-        loc = [p.t().contiguous() for p in self.pos]  # [nloc][dim]
-        if self.world == 1:
-            return torch.cat(loc, 0).cpu().numpy()
-        out = []
-        for h in (0, 1):
-            buf = torch.empty((self.world * self.nloc, self.dim), dtype=torch.float64, device=self.device)
-            torch.distributed.all_gather_into_tensor(buf, loc[h], group=self.group)
-            out.append(buf)
-        return torch.cat(out, 0).cpu().numpy()
+        return self._gather_halves([p.t().contiguous() for p in self.pos])
 
     def gather_lnprob(self):
-        torch = _torch()
-        if self.world == 1:
-            return torch.cat(self.lnp, 0).cpu().numpy()
-        out = []
-        for h in (0, 1):
-            buf = torch.empty(self.world * self.nloc, dtype=torch.float64, device=self.device)
-            torch.distributed.all_gather_into_tensor(buf, self.lnp[h].contiguous(), group=self.group)
-            out.append(buf)
-        return torch.cat(out, 0).cpu().numpy()
+        return self._gather_halves(self.lnp)
 
     def _gather_int(self, local):
         """[2*nloc] per-rank counters (half 0 slice | half 1 slice) -> [W] in global order."""
-        torch = _torch()
-        n = self.nloc
-        if self.world == 1:
+        if self.world == 1:  # (already in global order: no concatenation)
             return local.cpu().numpy()
-        out = []
-        for h in (0, 1):
-            buf = torch.empty(self.world * n, dtype=local.dtype, device=self.device)
-            torch.distributed.all_gather_into_tensor(buf, local[h * n:(h + 1) * n].contiguous(), group=self.group)
-            out.append(buf)
-        return torch.cat(out).cpu().numpy()
+        return self._gather_halves([local[:self.nloc], local[self.nloc:]])
 
     def checkpoint(self, path):
         """Save the whole ensemble (every rank takes part; rank 0 writes path, an .npz): positions

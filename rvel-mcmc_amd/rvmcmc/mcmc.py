@@ -17,7 +17,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib, chain, engine
+from . import _lib, engine
+from ._lib import _torch, ptr
 from .chain import ChainRecorder
 from .ensemble import EnsembleSampler
 from .state import Encounter
@@ -159,8 +160,7 @@ class Mh(Mcmc):
             self._buf = []
 
     def _fill(self):
-        import torch
-
+        torch = _torch()
         self._base_logp = self.state.get_logp(self.obs)
         entries, live = [], []
         for _ in range(self.speculate):
@@ -207,7 +207,7 @@ class Mh(Mcmc):
         return False
 
 
-class MhChains:
+class MhChains(engine.DeviceSampler):
     """n_chains independent Gaussian random-walk MH chains, all resident on the device.
 
     Per step ONE launch for all chains (rvm_mh_step: the likelihood kernel forms each chain's
@@ -216,8 +216,7 @@ class MhChains:
     semantics per chain; priorHard / Encounter proposals are rejected through logp = -inf)."""
 
     def __init__(self, initial_state, obs, scales, step_size, n_chains, X0=None, seed=0, device=None):
-        import torch
-
+        torch = _torch()
         self.state = initial_state.deepcopy()
         self.obs = obs
         self.dim = self.state.Nvars
@@ -225,12 +224,10 @@ class MhChains:
         self.step_size = float(step_size)
         self.seed = int(seed)
         self.iteration = 0
-        self.device = torch.device(device) if device is not None else engine.default_device()
+        self.device = engine.default_device(device)
         self.lib = _lib.load()
         self.pmap = self.state.param_map()
-        dt, mult, hint = self.state.integrator.plan_args(self.state.planets)
-        self.plan = engine.plan_for(obs, self.pmap.n_planets, dt, mult, self.n, self.device, hint, self.pmap.inclined,
-                                    self.state.integrator.resolve(self.state.planets))
+        self.plan = engine.plan_for_state(self.state, obs, self.n, self.device)
         self.scales = torch.as_tensor(_scales_vector(self.state, scales), device=self.device)
         if X0 is None:
             X0 = np.tile(self.state.get_params()[:, None], (1, self.n))
@@ -247,8 +244,7 @@ class MhChains:
                  iteration=self.iteration, seed=self.seed, step_size=self.step_size)
 
     def restore(self, path):
-        import torch
-
+        torch = _torch()
         d = np.load(path)
         if d["X"].shape != tuple(self.X.shape):
             raise ValueError("checkpoint was written for a different number of chains or parameters")
@@ -266,45 +262,28 @@ class MhChains:
         walker's planet lanes share the Box-Muller draws (rvm_logl.hip), and the fused launch is
         ahead (4096 chains: 15.3-15.6M vs 14.8-15.1M chain-steps/s, profiles/r02h_configs.jsonl).
         On the stream the chains were built on (engine.check_stream)."""
-        import torch
-
         engine.check_stream(self.plan, "MhChains.step")
-
         st = _lib.stream_handle()
         if fused and draws_propose is None and draws_accept is None:
-            with torch.cuda.device(self.device):
+            with _torch().cuda.device(self.device):
                 _lib.check(self.lib.rvm_mh_step(self.plan._h, C.byref(self.pmap.c_map()), self.dim, self.n, 0,
                                                 self.X.data_ptr(), self.lnp.data_ptr(), self.scales.data_ptr(),
                                                 self.step_size, self.seed, self.iteration,
                                                 float(self.state.hillRadiusFactor), 0, 0, self.accepted.data_ptr(),
                                                 st), "rvm_mh_step")
-            self.iteration += 1
-            engine.periodic_fault_check(self, self.plan)
-            return
-        _lib.check(self.lib.rvm_mh_propose(self.dim, self.n, 0, self.X.data_ptr(), self.scales.data_ptr(),
-                                           self.step_size, self.seed, self.iteration,
-                                           draws_propose.data_ptr() if draws_propose is not None else 0,
-                                           self.Q.data_ptr(), st), "rvm_mh_propose")
-        lnp_new, _, _ = self.plan.logl(self.pmap.to_kernel(self.Q), hill_factor=self.state.hillRadiusFactor)
-        _lib.check(self.lib.rvm_mh_accept(self.dim, self.n, 0, self.X.data_ptr(), self.lnp.data_ptr(),
-                                          self.Q.data_ptr(), lnp_new.data_ptr(), self.seed, self.iteration,
-                                          draws_accept.data_ptr() if draws_accept is not None else 0,
-                                          self.accepted.data_ptr(), st), "rvm_mh_accept")
-        self.iteration += 1
-        engine.periodic_fault_check(self, self.plan)
+        else:
+            _lib.check(self.lib.rvm_mh_propose(self.dim, self.n, 0, self.X.data_ptr(), self.scales.data_ptr(),
+                                               self.step_size, self.seed, self.iteration, ptr(draws_propose),
+                                               self.Q.data_ptr(), st), "rvm_mh_propose")
+            lnp_new, _, _ = self.plan.logl(self.pmap.to_kernel(self.Q), hill_factor=self.state.hillRadiusFactor)
+            _lib.check(self.lib.rvm_mh_accept(self.dim, self.n, 0, self.X.data_ptr(), self.lnp.data_ptr(),
+                                              self.Q.data_ptr(), lnp_new.data_ptr(), self.seed, self.iteration,
+                                              ptr(draws_accept), self.accepted.data_ptr(), st), "rvm_mh_accept")
+        self._end_step()
 
     def _chain_segments(self):
         """The chains, for chain.ChainRecorder."""
         return [dict(x=self.X, lnp=self.lnp, col0=0, n=self.n)]
-
-    def run_mcmc(self, n_steps, recorder=None):
-        """n_steps fused steps; every recorder.thin-th one goes into `recorder` (chain.ChainRecorder)."""
-        return chain.run_mcmc(self, n_steps, recorder)
-
-    def check_faults(self):
-        """rvm_plan_faults of the chains' plan: raises on hand-off timeouts / NONFINITE results."""
-        self.last_faults = self.plan.check_faults(type(self).__name__)
-        return self.last_faults
 
 
 from .smala import Alsmala, Smala, SmalaChains  # noqa: E402  (re-export with the reference's module layout)

@@ -27,6 +27,17 @@ class Observation:
     err = None
 
 
+class Epochs(Observation):
+    """A throw-away observation set that carries only epochs: what the model RV at `times` is
+    evaluated on (State.get_rv, ChainRecorder.predict)."""
+
+    def __init__(self, times):
+        self.tf, self.tb = times, np.zeros(0)
+        self.rvf, self.rvb = np.zeros(len(times)), np.zeros(0)
+        self.errorf, self.errorb = np.ones(len(times)), np.zeros(0)
+        self.Npoints = 1
+
+
 class FakeObservation(Observation):
     def __init__(self, state, Npoints=30, error=0., errorVar=0., tmax=1.5):
         self.Npoints = Npoints

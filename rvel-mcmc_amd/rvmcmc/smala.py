@@ -21,17 +21,12 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib, chain, engine
+from . import _lib, engine
+from ._lib import _torch
 
 # relative FD step and per-key absolute floors (h, k and l can be ~0)
 FD_REL_STEP = 1e-6
 FD_FLOOR = {"m": 1e-4, "a": 1e-2, "h": 1e-2, "k": 1e-2, "l": 1.0, "ix": 1e-2, "iy": 1e-2}
-
-
-def _torch():
-    import torch
-
-    return torch
 
 
 def fd_floor_vector(state):
@@ -51,13 +46,10 @@ def fd_logp_grad_metric(state, obs, X, rel_step=FD_REL_STEP, pmap=None, hill_fac
                                  stencil.data_ptr(), _lib.stream_handle()), "rvm_fd_params")
     # the stencil on the fixed-step plan (every point of a chain with the same steps:
     # SmalaChains._fixed_plan), the centres' logp from the adaptive one
-    it = state.integrator
-    dt, mult, hint = it.plan_args(state.planets)
-    plan = engine.plan_for(obs, len(state.planets), dt, mult, S * C_, X.device, hint, engine.is_inclined(state.planets),
-                           (0.0, 0))
+    plan = engine.plan_for_state(state, obs, S * C_, X.device, adaptive=False)
     hf = state.hillRadiusFactor if hill_factor is None else hill_factor
     lp, st, rv = plan.logl(pmap.to_kernel(stencil), hill_factor=hf, want_rv=True)
-    if it.resolve()[0] > 0.0:
+    if state.integrator.resolve()[0] > 0.0:
         lpc, stc, _ = state.get_logp_batch(obs, X.contiguous(), hill_factor=hill_factor, pmap=pmap)
         lp[:C_].copy_(lpc)
         st[:C_].copy_(stc)
@@ -82,7 +74,7 @@ def fd_logp_grad_metric(state, obs, X, rel_step=FD_REL_STEP, pmap=None, hill_fac
     return lp[0], grad, H, status
 
 
-class SmalaChains:
+class SmalaChains(engine.DeviceSampler):
     """C independent SMALA chains on the device (config 4: 256 chains).
 
     Per step (mcmc.py:167-187 for every chain at once): rvm_smala_propose, one likelihood launch
@@ -110,7 +102,7 @@ class SmalaChains:
         self.hessian = hessian
         self.rel_step = float(rel_step)
         self.seed = int(seed)
-        self.device = torch.device(device) if device is not None else engine.default_device()
+        self.device = engine.default_device(device)
         self.lib = _lib.load()
         self.pmap = self.state.param_map()
         self.floor = torch.as_tensor(fd_floor_vector(self.state), device=self.device)
@@ -149,11 +141,9 @@ class SmalaChains:
         the same steps -- a refinement of some points but not others (per-walker decisions) would
         put the resolution's change, up to the bound, into the difference quotient -- and the
         gradient and metric only shape the proposal (the MH test keeps the target exact); the
-        chain's logp itself comes from the adaptive plan (_center_logl)."""
-        it = self.state.integrator
-        dt, mult, hint = it.plan_args(self.state.planets)
-        return engine.plan_for(self.obs, len(self.state.planets), dt, mult, max_walkers, self.device, hint,
-                               engine.is_inclined(self.state.planets), (0.0, 0))
+        chain's logp itself comes from the adaptive plan (_center_start).  Looked up per launch, for
+        the stream current then."""
+        return engine.plan_for_state(self.state, self.obs, max_walkers, self.device, adaptive=False)
 
     def _center_plan(self):
         """The adaptive plan of the chains' own logp (on the side stream: _center_start), created at
@@ -162,7 +152,7 @@ class SmalaChains:
         if getattr(self, "_side", None) is None:
             self._side = torch.cuda.Stream(device=self.device)
         with torch.cuda.stream(self._side):
-            self._cplan = self.state._plan(self.obs, max_walkers=self.n, device=self.device)
+            self._cplan = engine.plan_for_state(self.state, self.obs, self.n, self.device)
         return self._cplan
 
     def _center_start(self, X):
@@ -185,28 +175,29 @@ class SmalaChains:
             done.record(self._side)
         return lpc, stc, done
 
+    def _center_wait(self, pending):
+        """The current stream waits for a pending centre launch (_center_start): its (logp, status),
+        allocated on the side stream and read on this one from here on."""
+        lpc, stc, done = pending
+        main = _torch().cuda.current_stream(self.device)
+        main.wait_event(done)
+        lpc.record_stream(main)
+        stc.record_stream(main)
+        return lpc, stc
+
     def _center_join(self, pending, lp, st):
         """Overwrite the stencil centres' logp / status (walkers 0 .. C-1) with the side stream's."""
-        if pending is None:
-            return
-        torch = _torch()
-        lpc, stc, done = pending
-        main = torch.cuda.current_stream(self.device)
-        main.wait_event(done)
-        lp[:self.n].copy_(lpc)
-        st[:self.n].copy_(stc)
-        lpc.record_stream(main)  # (allocated on the side stream, last read on this one)
-        stc.record_stream(main)
+        if pending is not None:
+            lpc, stc = self._center_wait(pending)
+            lp[:self.n].copy_(lpc)
+            st[:self.n].copy_(stc)
 
-    def _center_logl(self, X, lp, st):
-        self._center_join(self._center_start(X), lp, st)
-
-    def _stencil_logl(self, X, fused=True, join=True):
+    def _stencil_logl(self, X, fused=True):
         """logp, status [(2P+1) C] and model RVs [n_obs][(2P+1) C] over the central-difference
         stencil of X: one launch that forms the stencil in the likelihood kernel's prologue
         (rvm_smala_stencil_logl), or rvm_fd_params + rvm_logl_batch (fused=False; same bits), both
-        on the fixed-step plan (_fixed_plan); the centres' logp then from the adaptive plan
-        (join=False, fused only: not copied in; returned as the pending launch, or None)."""
+        on the fixed-step plan (_fixed_plan).  Fourth: the centres' pending launch on the adaptive
+        plan (_center_start; None when the resolution is off), for the caller to join."""
         torch = _torch()
         S = 2 * self.P + 1
         plan = self._fixed_plan(S * self.n)
@@ -215,41 +206,48 @@ class SmalaChains:
             _lib.check(self.lib.rvm_fd_params(self.P, self.n, X.data_ptr(), self.rel_step, self.floor.data_ptr(),
                                               self.stencil.data_ptr(), _lib.stream_handle()), "rvm_fd_params")
             lp, st, rv = plan.logl(self.pmap.to_kernel(self.stencil), hill_factor=1.0, want_rv=True)
-            self._plan_keep = plan
-            self._center_join(pending, lp, st)
-            return lp, st, rv
-        if getattr(self, "_st_bufs", None) is None:
-            self._st_bufs = (torch.empty(S * self.n, dtype=torch.float64, device=self.device),
-                             torch.empty(S * self.n, dtype=torch.int32, device=self.device),
-                             torch.empty((self.n_obs, S * self.n), dtype=torch.float64, device=self.device))
-        lp, st, rv = self._st_bufs
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rvm_smala_stencil_logl(plan._h, C.byref(self.pmap.c_map()), self.P, self.n,
-                                                       X.data_ptr(), self.rel_step, self.floor.data_ptr(), 1.0,
-                                                       lp.data_ptr(), st.data_ptr(), rv.data_ptr(),
-                                                       _lib.stream_handle()), "rvm_smala_stencil_logl")
+        else:
+            if getattr(self, "_st_bufs", None) is None:
+                self._st_bufs = (torch.empty(S * self.n, dtype=torch.float64, device=self.device),
+                                 torch.empty(S * self.n, dtype=torch.int32, device=self.device),
+                                 torch.empty((self.n_obs, S * self.n), dtype=torch.float64, device=self.device))
+            lp, st, rv = self._st_bufs
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.rvm_smala_stencil_logl(plan._h, C.byref(self.pmap.c_map()), self.P, self.n,
+                                                           X.data_ptr(), self.rel_step, self.floor.data_ptr(), 1.0,
+                                                           lp.data_ptr(), st.data_ptr(), rv.data_ptr(),
+                                                           _lib.stream_handle()), "rvm_smala_stencil_logl")
         self._plan_keep = plan  # the launch's plan stays alive with the sampler
-        if not join:
-            return lp, st, rv, pending
+        return lp, st, rv, pending
+
+    def _exact_derivs(self, X):
+        """Exact logp, gradient, Hessian and status of X (rvm_logl_derivs), the logp and status
+        overwritten with the adaptive plan's, whose launch runs beside the derivative launch."""
+        pending = self._center_start(X)
+        lp, g, H, st = self.state.get_logp_d_dd_batch(self.obs, X, hill_factor=1.0, pmap=self.pmap)
         self._center_join(pending, lp, st)
-        return lp, st, rv
+        self._keep = (lp, g, H, st)  # alive until the stream has consumed them
+        return self._keep
+
+    def _derive(self, fn, X, lp, st, rv, cache):
+        """rvm_smala_derive, or rvm_smala_derive_sides (everything but the two cache entries that
+        depend on the stencil's centre row): the FD gradient, Gauss-Newton Hessian, SoftAbs metric,
+        Cholesky factor and drift of X into `cache`."""
+        _lib.check(getattr(self.lib, fn)(self.P, self.n, self.n_obs, X.data_ptr(), self.rel_step,
+                                         self.floor.data_ptr(), lp.data_ptr(), st.data_ptr(), rv.data_ptr(),
+                                         self.inv_sigma2.data_ptr(), float(self.obs.Npoints), self.alpha, self.eps,
+                                         C.byref(cache["_c"]), _lib.stream_handle()), fn)
 
     def _derive_into(self, X, cache, fused=True):
-        st_h = _lib.stream_handle()
         if self.hessian == "exact":
-            pending = self._center_start(X)  # (the adaptive logp beside the derivative launch)
-            lp, g, H, st = self.state.get_logp_d_dd_batch(self.obs, X, hill_factor=1.0, pmap=self.pmap)
-            self._center_join(pending, lp, st)
+            lp, g, H, st = self._exact_derivs(X)
             _lib.check(self.lib.rvm_smala_metric(self.P, self.n, X.data_ptr(), lp.data_ptr(), st.data_ptr(),
                                                  g.data_ptr(), H.data_ptr(), self.alpha, self.eps,
-                                                 C.byref(cache["_c"]), st_h), "rvm_smala_metric")
-            self._keep = (lp, g, H, st)  # alive until the stream has consumed them
+                                                 C.byref(cache["_c"]), _lib.stream_handle()), "rvm_smala_metric")
             return
-        lp, st, rv = self._stencil_logl(X, fused)
-        _lib.check(self.lib.rvm_smala_derive(self.P, self.n, self.n_obs, X.data_ptr(), self.rel_step,
-                                             self.floor.data_ptr(), lp.data_ptr(), st.data_ptr(), rv.data_ptr(),
-                                             self.inv_sigma2.data_ptr(), float(self.obs.Npoints), self.alpha,
-                                             self.eps, C.byref(cache["_c"]), st_h), "rvm_smala_derive")
+        lp, st, rv, pending = self._stencil_logl(X, fused)
+        self._center_join(pending, lp, st)
+        self._derive("rvm_smala_derive", X, lp, st, rv, cache)
 
     def checkpoint(self, path):
         """Chains, counters, iteration and seed to an .npz.  The per-chain derivative caches are not
@@ -282,86 +280,50 @@ class SmalaChains:
         (rvm_smala_metric_accept) -- with the centres on the adaptive plan, rvm_smala_derive_sides
         beside the centres' launch and rvm_smala_center_accept after it; fused=False runs the separate
         fd / logl / derive / accept launches (bit-identical; 256 chains: 523k vs 485k chain-steps/s fused vs separate,
-        profiles/r02h_configs.jsonl).  The plan is looked up per step for the current stream
-        (State._plan -> engine.plan_for), so any stream is safe."""
+        profiles/r02h_configs.jsonl).  The plans are looked up per step for the current stream
+        (engine.plan_for_state), so any stream is safe."""
         st_h = _lib.stream_handle()
-        zp = 0
+        zp = up = 0
         if z is not None:
             self._z = z.t().contiguous()
             zp = self._z.data_ptr()
-        up = 0
         if u is not None:
             self._u = u.contiguous()
             up = self._u.data_ptr()
-        _lib.check(self.lib.rvm_smala_propose(self.P, self.n, 0, self.X.data_ptr(), C.byref(self.cache["_c"]),
-                                              self.eps, self.seed, self.iteration, zp, self.Xs.data_ptr(), st_h),
-                   "rvm_smala_propose")
-        cur, prop = C.byref(self.cache["_c"]), C.byref(self.prop["_c"])
-        if fused and self.hessian == "exact":
-            pending = self._center_start(self.Xs)  # (the logp the accept uses: adaptive resolution)
-            lp, g, H, st = self.state.get_logp_d_dd_batch(self.obs, self.Xs, hill_factor=1.0, pmap=self.pmap)
-            self._center_join(pending, lp, st)
-            _lib.check(self.lib.rvm_smala_metric_accept(self.P, self.n, 0, self.X.data_ptr(), self.Xs.data_ptr(),
-                                                        lp.data_ptr(), st.data_ptr(), g.data_ptr(), H.data_ptr(),
-                                                        self.alpha, self.eps, cur, prop, self.seed, self.iteration,
-                                                        up, self.accepted.data_ptr(), self.failures.data_ptr(),
-                                                        st_h), "rvm_smala_metric_accept")
-            self._keep = (lp, g, H, st)
-            self.iteration += 1
-            self._periodic_faults()
-            return
-        if fused:
-            lp, st, rv, pending = self._stencil_logl(self.Xs, join=False)
+        X, Xs, cur, prop = self.X.data_ptr(), self.Xs.data_ptr(), C.byref(self.cache["_c"]), C.byref(self.prop["_c"])
+        _lib.check(self.lib.rvm_smala_propose(self.P, self.n, 0, X, cur, self.eps, self.seed, self.iteration, zp, Xs,
+                                              st_h), "rvm_smala_propose")
+        # what every accept launch ends with: the draws' key, the injected uniforms, the counters, the stream
+        tail = (self.seed, self.iteration, up, self.accepted.data_ptr(), self.failures.data_ptr(), st_h)
+        if not fused:
+            self._derive_into(self.Xs, self.prop, fused=False)
+            _lib.check(self.lib.rvm_smala_accept(self.P, self.n, 0, X, cur, Xs, prop, self.eps, *tail),
+                       "rvm_smala_accept")
+        elif self.hessian == "exact":
+            lp, g, H, st = self._exact_derivs(self.Xs)  # (the logp the accept uses: adaptive resolution)
+            _lib.check(self.lib.rvm_smala_metric_accept(self.P, self.n, 0, X, Xs, lp.data_ptr(), st.data_ptr(),
+                                                        g.data_ptr(), H.data_ptr(), self.alpha, self.eps, cur, prop,
+                                                        *tail), "rvm_smala_metric_accept")
+        else:
+            lp, st, rv, pending = self._stencil_logl(self.Xs)
             if pending is not None:
                 # the proposal's derivatives and metric from the stencil's sides while the centres'
                 # adaptive launch (and its halving passes) still runs on the side stream; the accept
                 # once it is done, with the centres' own logp and status (no copies; same bits)
-                torch = _torch()
-                _lib.check(self.lib.rvm_smala_derive_sides(
-                    self.P, self.n, self.n_obs, self.Xs.data_ptr(), self.rel_step, self.floor.data_ptr(),
-                    lp.data_ptr(), st.data_ptr(), rv.data_ptr(), self.inv_sigma2.data_ptr(),
-                    float(self.obs.Npoints), self.alpha, self.eps, prop, st_h), "rvm_smala_derive_sides")
-                lpc, stc, done = pending
-                main = torch.cuda.current_stream(self.device)
-                main.wait_event(done)
-                _lib.check(self.lib.rvm_smala_center_accept(
-                    self.P, self.n, 0, self.X.data_ptr(), self.Xs.data_ptr(), lpc.data_ptr(), stc.data_ptr(), cur,
-                    prop, self.eps, self.seed, self.iteration, up, self.accepted.data_ptr(),
-                    self.failures.data_ptr(), st_h), "rvm_smala_center_accept")
-                lpc.record_stream(main)  # (allocated on the side stream, last read on this one)
-                stc.record_stream(main)
-                self.iteration += 1
-                self._periodic_faults()
-                return
-            _lib.check(self.lib.rvm_smala_derive_accept(
-                self.P, self.n, 0, self.n_obs, self.X.data_ptr(), self.Xs.data_ptr(), self.rel_step,
-                self.floor.data_ptr(), lp.data_ptr(), st.data_ptr(), rv.data_ptr(), self.inv_sigma2.data_ptr(),
-                float(self.obs.Npoints), self.alpha, self.eps, cur, prop, self.seed, self.iteration, up,
-                self.accepted.data_ptr(), self.failures.data_ptr(), st_h), "rvm_smala_derive_accept")
-            self.iteration += 1
-            self._periodic_faults()
-            return
-        self._derive_into(self.Xs, self.prop, fused=False)
-        _lib.check(self.lib.rvm_smala_accept(self.P, self.n, 0, self.X.data_ptr(), C.byref(self.cache["_c"]),
-                                             self.Xs.data_ptr(), C.byref(self.prop["_c"]), self.eps, self.seed,
-                                             self.iteration, up, self.accepted.data_ptr(), self.failures.data_ptr(),
-                                             st_h), "rvm_smala_accept")
-        self.iteration += 1
-        self._periodic_faults()
-
+                self._derive("rvm_smala_derive_sides", self.Xs, lp, st, rv, self.prop)
+                lpc, stc = self._center_wait(pending)
+                _lib.check(self.lib.rvm_smala_center_accept(self.P, self.n, 0, X, Xs, lpc.data_ptr(), stc.data_ptr(),
+                                                            cur, prop, self.eps, *tail), "rvm_smala_center_accept")
+            else:
+                _lib.check(self.lib.rvm_smala_derive_accept(
+                    self.P, self.n, 0, self.n_obs, X, Xs, self.rel_step, self.floor.data_ptr(), lp.data_ptr(),
+                    st.data_ptr(), rv.data_ptr(), self.inv_sigma2.data_ptr(), float(self.obs.Npoints), self.alpha,
+                    self.eps, cur, prop, *tail), "rvm_smala_derive_accept")
+        self._end_step()
 
     def _chain_segments(self):
         """The chains and their cached logp, for chain.ChainRecorder."""
         return [dict(x=self.X, lnp=self.cache["lp"], col0=0, n=self.n)]
-
-    def run_mcmc(self, n_steps, recorder=None):
-        """n_steps fused steps; every recorder.thin-th one goes into `recorder` (chain.ChainRecorder)."""
-        return chain.run_mcmc(self, n_steps, recorder)
-
-    def _periodic_faults(self):  # (engine.periodic_fault_check over both plans)
-        every = getattr(self, "fault_check_every", engine.FAULT_CHECK_EVERY)
-        if every and self.iteration % every == 0:
-            self.check_faults()
 
     def check_faults(self):
         """rvm_plan_faults of the chains' plans (the centres' adaptive one, on its side stream, and the

@@ -24,6 +24,8 @@ import logging
 import numpy as np
 
 from . import engine
+from ._lib import _torch
+from .observations import Epochs
 
 log = logging.getLogger(__name__)
 
@@ -166,25 +168,12 @@ class State(object):
         return r
 
     def _plan(self, obs, max_walkers=1, device=None):
-        dt, mult, hint = self.integrator.plan_args(self.planets)
-        return engine.plan_for(obs, len(self.planets), dt, mult, max_walkers, device, hint,
-                               engine.is_inclined(self.planets), self.integrator.resolve(self.planets))
+        return engine.plan_for_state(self, obs, max_walkers, device)
 
     def get_rv(self, times):
         """state.py:61-73: model RV (star barycentric vx) at `times`; raises Encounter."""
-        import torch
-
-        times = np.asarray(times, dtype=np.float64)
-
-        class _T:  # a throw-away observation set carrying only the epochs
-            pass
-
-        o = _T()
-        o.tf, o.tb = times, np.zeros(0)
-        o.rvf, o.rvb = np.zeros(len(times)), np.zeros(0)
-        o.errorf, o.errorb = np.ones(len(times)), np.zeros(0)
-        o.Npoints = 1
-        plan = self._plan(o)
+        torch = _torch()
+        plan = self._plan(Epochs(np.asarray(times, dtype=np.float64)))
         K = torch.as_tensor(self.param_map().vector_to_kernel_np(self.get_params()), device=plan.device)[:, None]
         _, st, rv = plan.logl(K.contiguous(), hill_factor=self.hillRadiusFactor, want_rv=True)
         st = int(st.item())
@@ -197,8 +186,7 @@ class State(object):
         return times, self.get_rv(times)
 
     def _eval(self, obs):
-        import torch
-
+        torch = _torch()
         plan = self._plan(obs)
         K = torch.as_tensor(self.param_map().vector_to_kernel_np(self.get_params()), device=plan.device)[:, None]
         lp, st, _ = plan.logl(K.contiguous(), hill_factor=self.hillRadiusFactor)
@@ -248,8 +236,7 @@ class State(object):
 
     def get_chi2_d_dd(self, obs):  # state.py:253-288
         """(chi2, dchi2, d2chi2) ÷ obs.Npoints at the current parameters; raises Encounter."""
-        import torch
-
+        torch = _torch()
         x = torch.as_tensor(self.get_params(), dtype=torch.float64, device=engine.default_device())[:, None]
         lp, g, H, st = self.get_logp_d_dd_batch(obs, x)
         st = int(st[0].item())
@@ -266,8 +253,8 @@ class State(object):
         if self.logp is None or self.logp_d is None:
             if method == "fd":
                 from .smala import fd_logp_grad_metric
-                import torch
 
+                torch = _torch()
                 x = torch.as_tensor(self.get_params(), dtype=torch.float64, device=engine.default_device())[:, None]
                 lp, g, H, st = fd_logp_grad_metric(self, obs, x, rel_step=rel_step)
                 if int(st[0].item()) == 2:

@@ -44,13 +44,9 @@ import math
 
 import numpy as np
 
-from . import _lib, chain, engine
-
-
-def _torch():
-    import torch
-
-    return torch
+from . import _lib, engine
+from ._lib import _torch, ptr
+from .ensemble import check_walker_count
 
 
 def default_betas(ntemps, dim):
@@ -108,7 +104,7 @@ def log_evidence_ratio(betas, mean_lnp):
     return trapezoid(fine), trapezoid(coarse)
 
 
-class PTSampler:
+class PTSampler(engine.DeviceSampler):
     def __init__(self, ntemps, nwalkers, state, obs, betas=None, a=2.0, seed=0, device=None, hill_factor=None,
                  swap_every=1, adapt=False, adaptation_lag=10000, adaptation_time=100):
         # value checks first: nothing below them touches the device
@@ -116,10 +112,7 @@ class PTSampler:
         ntemps, nwalkers = int(ntemps), int(nwalkers)
         if ntemps < 1:
             raise ValueError("ntemps must be at least 1")
-        if nwalkers % 2 != 0:
-            raise ValueError("The number of walkers must be even.")
-        if nwalkers < 2 * dim:
-            raise ValueError("The number of walkers needs to be more than twice the dimension of your parameter space.")
+        check_walker_count(nwalkers, dim)
         self.betas = check_betas(default_betas(ntemps, dim) if betas is None else betas, ntemps)
         if not float(a) > 1.0:
             raise ValueError("the stretch scale a must be > 1")
@@ -143,11 +136,9 @@ class PTSampler:
         self.state, self.obs = state, obs
         self.pmap = state.param_map()
         self.hill_factor = state.hillRadiusFactor if hill_factor is None else float(hill_factor)
-        self.device = torch.device(device) if device is not None else engine.default_device()
+        self.device = engine.default_device(device)
         self.lib = _lib.load()
-        dt, mult, hint = state.integrator.plan_args(state.planets)
-        self.plan = engine.plan_for(obs, self.pmap.n_planets, dt, mult, self.n, self.device, hint, self.pmap.inclined,
-                                    state.integrator.resolve(state.planets))
+        self.plan = engine.plan_for_state(state, obs, self.n, self.device)
         f64 = dict(dtype=torch.float64, device=self.device)
         i32 = dict(dtype=torch.int32, device=self.device)
         self._betas = torch.as_tensor(self.betas, device=self.device)
@@ -230,15 +221,15 @@ class PTSampler:
         dp, da = self._dev(u12, (2, self.n)), self._dev(u3, (self.n,))
         sh = _lib.stream_handle()
         _lib.check(self.lib.rvm_pt_stretch_propose(self.dim, self.ntemps, self.halfk, X0.data_ptr(), c.data_ptr(),
-                                                   self.a, self.seed, self.iteration, half,
-                                                   dp.data_ptr() if dp is not None else 0, self._q.data_ptr(),
-                                                   self._z.data_ptr(), sh), "rvm_pt_stretch_propose")
+                                                   self.a, self.seed, self.iteration, half, ptr(dp),
+                                                   self._q.data_ptr(), self._z.data_ptr(), sh),
+                   "rvm_pt_stretch_propose")
         self._logl(self._q, out=self._lnp_new, status=self._status)
         _lib.check(self.lib.rvm_pt_stretch_accept(self.dim, self.ntemps, self.halfk, self._betas.data_ptr(),
                                                   X0.data_ptr(), lnp0.data_ptr(), self._q.data_ptr(),
                                                   self._lnp_new.data_ptr(), self._z.data_ptr(), self.seed,
-                                                  self.iteration, half, da.data_ptr() if da is not None else 0,
-                                                  self.naccepted[half].data_ptr(), sh), "rvm_pt_stretch_accept")
+                                                  self.iteration, half, ptr(da), self.naccepted[half].data_ptr(), sh),
+                   "rvm_pt_stretch_accept")
 
     def swap(self, u=None):
         """One exchange sweep over the neighbouring temperature pairs, hottest pair first.
@@ -246,9 +237,8 @@ class PTSampler:
         du = self._dev(u, (max(self.ntemps - 1, 0), self.k))
         _lib.check(self.lib.rvm_pt_swap(self.dim, self.ntemps, self.halfk, self._betas.data_ptr(),
                                         self.pos[0].data_ptr(), self.pos[1].data_ptr(), self.lnp[0].data_ptr(),
-                                        self.lnp[1].data_ptr(), self.seed, self.iteration,
-                                        du.data_ptr() if du is not None else 0, self.nswapped.data_ptr(),
-                                        _lib.stream_handle()), "rvm_pt_swap")
+                                        self.lnp[1].data_ptr(), self.seed, self.iteration, ptr(du),
+                                        self.nswapped.data_ptr(), _lib.stream_handle()), "rvm_pt_swap")
         self.nswaps += 1
 
     def _ladder_update(self, kappa, moments):
@@ -295,8 +285,7 @@ class PTSampler:
         if self.recording:
             self._ladder_update(0.0, True)  # kappa = 0: the betas stay bit for bit
             self.nrecorded += 1
-        self.iteration += 1
-        engine.periodic_fault_check(self, self.plan)
+        self._end_step()
 
     def _chain_segments(self):
         """The coldest temperature (beta = betas[0]) for chain.ChainRecorder: the first W/2 columns of
@@ -304,17 +293,6 @@ class PTSampler:
         if self.pos is None:
             raise ValueError("set_positions first")
         return [dict(x=self.pos[h], lnp=self.lnp[h], col0=0, n=self.halfk) for h in (0, 1)]
-
-    def run_mcmc(self, n_steps, recorder=None):
-        """n_steps iterations; every recorder.thin-th one goes into `recorder` (chain.ChainRecorder)."""
-        return chain.run_mcmc(self, n_steps, recorder)
-
-    def check_faults(self):
-        """Raise on level-split hand-off timeouts, NONFINITE or UNRESOLVED log-likelihoods since the
-        last check (rvm_plan_faults; also run every FAULT_CHECK_EVERY iterations by step());
-        returns the counters, including the walker-directions the adaptive resolution refined."""
-        self.last_faults = self.plan.check_faults(type(self).__name__)
-        return self.last_faults
 
     # ---- results (host numpy) --------------------------------------------------------------------
     def positions(self):
