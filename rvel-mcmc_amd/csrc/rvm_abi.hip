@@ -73,25 +73,56 @@ int rvm::hip_fail(hipError_t e, const char* where) {
     return fail(-3, std::string(where) + ": " + hipGetErrorString(e));
 }
 
-using rvm::fail;
-using rvm::hip_fail;
+using rvm::Entry;
+
+// ---- the rules more than one entry point checks: the refusal's text, or null ----
+static const char* bad_hill(double hill_factor) { return hill_factor >= 0.0 ? nullptr : "hill_factor must be >= 0"; }
+static const char* bad_scale(double a) { return a > 1.0 ? nullptr : "stretch scale a must be > 1"; }
+static const char* bad_window(int64_t t0, int64_t t1) {  // the steps [t0, t1) of a recorded chain
+    return t0 < 0 ? "t0 must be >= 0" : t1 <= t0 ? "t1 must be > t0" : nullptr;
+}
+// this rank's n_loc walkers of half 0 from s0_begin and of half 1 from s1_begin (global indices)
+static const char* bad_halves(int32_t n_loc, int32_t n_half, int64_t s0_begin, int64_t s1_begin) {
+    if (s0_begin < 0 || s0_begin + n_loc > n_half || s1_begin < n_half || s1_begin + n_loc > 2 * (int64_t)n_half)
+        return "walker ranges outside the halves";
+    return nullptr;
+}
 
 // parameter rows of the plan's launches (rvm_param_map::n_rows; rvm_logl_derivs' dir_rows index them)
 static int plan_rows(const rvm_plan* plan) { return (plan->dev.inclined ? 7 : 5) * plan->dev.n_planets; }
 
-// The map's row count against the plan's, then the map into sa->src / sa->base.  Returns 0 or the
-// refusal, its message prefixed with the caller's name.
-static int fill_map(const char* who, const rvm_plan* plan, const rvm_param_map* map, int32_t n_params,
+// The map's row count against the plan's, then the map into sa->src / sa->base.  Returns 0 or the refusal.
+static int fill_map(const Entry& at, const rvm_plan* plan, const rvm_param_map* map, int32_t n_params,
                     rvm::StretchArgs* sa) {
     const int rows = plan_rows(plan);
-    if (map->n_rows != rows) return fail(-1, std::string(who) + ": map rows do not match the plan");
+    if (map->n_rows != rows) return at.bad("map rows do not match the plan");
     for (int r = 0; r < RVM_MAX_PARAM_ROWS; r++) {
         const int k = r < rows ? map->src[r] : -1;
-        if (k >= n_params) return fail(-1, std::string(who) + ": map source index out of range");
+        if (k >= n_params) return at.bad("map source index out of range");
         sa->src[r] = k < 0 ? -1 : k;
         sa->base[r] = r < rows ? map->base[r] : 0.0;
     }
     return 0;
+}
+
+// the fields the fused sampler launches share: the n walkers of x (lnp, accepted) from global index
+// s0_begin, and for the stretch move the n1 walkers of c they are proposed against (MH: none, zeros)
+static void fill_stretch(rvm::StretchArgs* sa, int32_t n_params, int32_t n, int64_t s0_begin, double* x, double* x_aos,
+                         double* lnp, int32_t n1, const double* c, double a, uint64_t seed, uint64_t iteration,
+                         uint32_t half, int32_t* accepted) {
+    sa->c = c;
+    sa->x = x;
+    sa->x_aos = x_aos;
+    sa->lnp = lnp;
+    sa->accepted = accepted;
+    sa->s0_begin = s0_begin;
+    sa->seed = seed;
+    sa->iteration = iteration;
+    sa->a = a;
+    sa->n1 = n1;
+    sa->dim = n_params;
+    sa->half = half;
+    sa->xstride = n;
 }
 
 extern "C" {
@@ -101,46 +132,31 @@ int rvm_abi_version(void) { return RVM_ABI_VERSION; }
 
 int rvm_logl_batch(const rvm_plan* plan, int32_t n_walkers, const double* params, double hill_factor,
                    double* logl_out, int32_t* status_out, double* rv_out, void* stream) {
-    if (!plan) return fail(-1, "rvm_logl_batch: null plan");
+    const Entry at{"rvm_logl_batch"};
+    if (!plan) return at.null("plan");
     if (n_walkers == 0) return 0;
-    if (n_walkers < 0 || n_walkers > plan->max_walkers)
-        return fail(-1, "rvm_logl_batch: n_walkers exceeds the plan's max_walkers");
-    if (!params || !logl_out || !status_out) return fail(-1, "rvm_logl_batch: null buffer");
-    if (!(hill_factor >= 0.0)) return fail(-1, "rvm_logl_batch: hill_factor must be >= 0");
+    if (n_walkers < 0 || n_walkers > plan->max_walkers) return at.bad("n_walkers exceeds the plan's max_walkers");
+    if (!params || !logl_out || !status_out) return at.null("buffer");
+    if (const char* m = bad_hill(hill_factor)) return at.bad(m);
     rvm::StretchArgs none{};
-    hipError_t e = run_logl(plan, n_walkers, params, hill_factor, logl_out, status_out, rv_out, none, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "rvm_logl_batch");
-    return 0;
+    return at.done(run_logl(plan, n_walkers, params, hill_factor, logl_out, status_out, rv_out, none, (hipStream_t)stream));
 }
 
 int rvm_stretch_half_step(const rvm_plan* plan, const rvm_param_map* map, int32_t n_params, int32_t n_s0,
                           int64_t s0_begin, double* x, double* x_aos, double* lnp, int32_t n_s1, const double* c,
                           double a, uint64_t seed, uint64_t iteration, uint32_t half, double hill_factor,
                           double* lnp_new_out, int32_t* status_out, int32_t* accepted, void* stream) {
-    if (!plan || !map) return fail(-1, "rvm_stretch_half_step: null plan or map");
+    const Entry at{"rvm_stretch_half_step"};
+    if (!plan || !map) return at.null("plan or map");
     if (n_s0 == 0) return 0;
-    if (n_s0 < 0 || n_s0 > plan->max_walkers)
-        return fail(-1, "rvm_stretch_half_step: n_s0 exceeds the plan's max_walkers");
-    if (n_params < 1 || n_s1 < 1 || !x || !lnp || !c) return fail(-1, "rvm_stretch_half_step: bad arguments");
-    if (!(a > 1.0)) return fail(-1, "rvm_stretch_half_step: stretch scale a must be > 1");
-    if (!(hill_factor >= 0.0)) return fail(-1, "rvm_stretch_half_step: hill_factor must be >= 0");
+    if (n_s0 < 0 || n_s0 > plan->max_walkers) return at.bad("n_s0 exceeds the plan's max_walkers");
+    if (n_params < 1 || n_s1 < 1 || !x || !lnp || !c) return at.bad("bad arguments");
+    if (const char* m = bad_scale(a)) return at.bad(m);
+    if (const char* m = bad_hill(hill_factor)) return at.bad(m);
     rvm::StretchArgs sa{};
-    if (const int rc = fill_map("rvm_stretch_half_step", plan, map, n_params, &sa)) return rc;
-    sa.c = c;
-    sa.x = x;
-    sa.x_aos = x_aos;
-    sa.lnp = lnp;
-    sa.accepted = accepted;
-    sa.s0_begin = s0_begin;
-    sa.seed = seed;
-    sa.iteration = iteration;
-    sa.a = a;
-    sa.n1 = n_s1;
-    sa.dim = n_params;
-    sa.half = half;
-    sa.xstride = n_s0;
-    hipError_t e = run_logl(plan, n_s0, nullptr, hill_factor, lnp_new_out, status_out, nullptr, sa, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_stretch_half_step");
+    if (const int rc = fill_map(at, plan, map, n_params, &sa)) return rc;
+    fill_stretch(&sa, n_params, n_s0, s0_begin, x, x_aos, lnp, n_s1, c, a, seed, iteration, half, accepted);
+    return at.done(run_logl(plan, n_s0, nullptr, hill_factor, lnp_new_out, status_out, nullptr, sa, (hipStream_t)stream));
 }
 
 int rvm_stretch_iteration_begin(const rvm_plan* plan, const rvm_param_map* map, int32_t n_params, int32_t n_loc,
@@ -148,39 +164,26 @@ int rvm_stretch_iteration_begin(const rvm_plan* plan, const rvm_param_map* map, 
                                 const double* lnp1, int32_t n_half, const double* c0, const double* c1, double a,
                                 uint64_t seed, uint64_t iteration, double hill_factor, double* lnp_spec,
                                 int32_t* status_spec, int32_t* dec, int32_t* accepted0, void* stream) {
-    if (!plan || !map) return fail(-1, "rvm_stretch_iteration_begin: null plan or map");
+    const Entry at{"rvm_stretch_iteration_begin"};
+    if (!plan || !map) return at.null("plan or map");
     if (n_loc == 0) return 0;
-    if (n_loc < 0 || (int64_t)3 * n_loc > plan->max_walkers)
-        return fail(-1, "rvm_stretch_iteration_begin: 3 n_loc exceeds the plan's max_walkers");
+    if (n_loc < 0 || (int64_t)3 * n_loc > plan->max_walkers) return at.bad("3 n_loc exceeds the plan's max_walkers");
     if (n_params < 1 || n_half < n_loc || !x0 || !lnp0 || !x1 || !c0 || !c1 || !lnp_spec || !status_spec || !dec)
-        return fail(-1, "rvm_stretch_iteration_begin: bad arguments");
-    if (s0_begin < 0 || s0_begin + n_loc > n_half || s1_begin < n_half || s1_begin + n_loc > 2 * (int64_t)n_half)
-        return fail(-1, "rvm_stretch_iteration_begin: walker ranges outside the halves");
-    if (!(a > 1.0)) return fail(-1, "rvm_stretch_iteration_begin: stretch scale a must be > 1");
-    if (!(hill_factor >= 0.0)) return fail(-1, "rvm_stretch_iteration_begin: hill_factor must be >= 0");
+        return at.bad("bad arguments");
+    if (const char* m = bad_halves(n_loc, n_half, s0_begin, s1_begin)) return at.bad(m);
+    if (const char* m = bad_scale(a)) return at.bad(m);
+    if (const char* m = bad_hill(hill_factor)) return at.bad(m);
     rvm::StretchArgs sa{};
-    if (const int rc = fill_map("rvm_stretch_iteration_begin", plan, map, n_params, &sa)) return rc;
-    sa.c = c1;
-    sa.x = x0;
-    sa.x_aos = nullptr;  // c0 must stay as it was until rvm_stretch_iteration_end
-    sa.lnp = lnp0;
-    sa.accepted = accepted0;
-    sa.s0_begin = s0_begin;
-    sa.seed = seed;
-    sa.iteration = iteration;
-    sa.a = a;
-    sa.n1 = n_half;
-    sa.dim = n_params;
-    sa.half = 0;
-    sa.xstride = n_loc;
+    if (const int rc = fill_map(at, plan, map, n_params, &sa)) return rc;
+    // (no walker-major mirror of x0: c0 must stay as it was until rvm_stretch_iteration_end)
+    fill_stretch(&sa, n_params, n_loc, s0_begin, x0, nullptr, lnp0, n_half, c1, a, seed, iteration, 0, accepted0);
     sa.n_spec = n_loc;
     sa.c0 = c0;
     sa.x1 = x1;
     sa.s1_begin = s1_begin;
     sa.dec = dec;
     sa.lnp1 = lnp1;
-    hipError_t e = run_logl(plan, 3 * n_loc, nullptr, hill_factor, lnp_spec, status_spec, nullptr, sa, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_stretch_iteration_begin");
+    return at.done(run_logl(plan, 3 * n_loc, nullptr, hill_factor, lnp_spec, status_spec, nullptr, sa, (hipStream_t)stream));
 }
 
 int rvm_stretch_iteration_end(int32_t n_params, int32_t n_loc, int64_t s0_begin, int64_t s1_begin, const double* x0,
@@ -189,13 +192,13 @@ int rvm_stretch_iteration_end(int32_t n_params, int32_t n_loc, int64_t s0_begin,
                               const double* lnp_spec, const int32_t* status_spec, double a, uint64_t seed,
                               uint64_t iteration, int32_t* accepted1, double* lnp_new_out, int32_t* status_new_out,
                               void* stream) {
+    const Entry at{"rvm_stretch_iteration_end"};
     if (n_loc == 0) return 0;
     if (n_params < 1 || n_loc < 0 || n_half < n_loc || !x0 || !dec || !dec_all || !x1 || !lnp1 || !c0 || !c1 ||
         !lnp_spec || !status_spec)
-        return fail(-1, "rvm_stretch_iteration_end: bad arguments");
-    if (s0_begin < 0 || s0_begin + n_loc > n_half || s1_begin < n_half || s1_begin + n_loc > 2 * (int64_t)n_half)
-        return fail(-1, "rvm_stretch_iteration_end: walker ranges outside the halves");
-    if (!(a > 1.0)) return fail(-1, "rvm_stretch_iteration_end: stretch scale a must be > 1");
+        return at.bad("bad arguments");
+    if (const char* m = bad_halves(n_loc, n_half, s0_begin, s1_begin)) return at.bad(m);
+    if (const char* m = bad_scale(a)) return at.bad(m);
     rvm::IterEndArgs g{};
     g.dim = n_params;
     g.n = n_loc;
@@ -219,31 +222,28 @@ int rvm_stretch_iteration_end(int32_t n_params, int32_t n_loc, int64_t s0_begin,
     g.accepted1 = accepted1;
     g.lnp_new_out = lnp_new_out;
     g.status_new_out = status_new_out;
-    hipError_t e = rvm::launch_stretch_iteration_end(g, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_stretch_iteration_end");
+    return at.done(rvm::launch_stretch_iteration_end(g, (hipStream_t)stream));
 }
 
 int rvm_stretch_propose(int32_t n_params, int32_t n_s0, int64_t s0_begin, const double* x, int32_t n_s1,
                         const double* c, double a, uint64_t seed, uint64_t iteration, uint32_t half,
                         const double* draws, double* q_out, double* z_out, void* stream) {
+    const Entry at{"rvm_stretch_propose"};
     if (n_s0 == 0) return 0;
-    if (n_params < 1 || n_s0 < 0 || n_s1 < 1 || !x || !c || !q_out || !z_out)
-        return fail(-1, "rvm_stretch_propose: bad arguments");
-    if (!(a > 1.0)) return fail(-1, "rvm_stretch_propose: stretch scale a must be > 1");
-    hipError_t e = rvm::launch_stretch_propose(n_params, n_s0, s0_begin, x, n_s1, c, a, seed, iteration, half, draws,
-                                               q_out, z_out, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_stretch_propose");
+    if (n_params < 1 || n_s0 < 0 || n_s1 < 1 || !x || !c || !q_out || !z_out) return at.bad("bad arguments");
+    if (const char* m = bad_scale(a)) return at.bad(m);
+    return at.done(rvm::launch_stretch_propose(n_params, n_s0, s0_begin, x, n_s1, c, a, seed, iteration, half, draws,
+                                               q_out, z_out, (hipStream_t)stream));
 }
 
 int rvm_stretch_accept(int32_t n_params, int32_t n_s0, int64_t s0_begin, double* x, double* lnp, const double* q,
                        const double* lnp_new, const double* z, uint64_t seed, uint64_t iteration, uint32_t half,
                        const double* draws, int32_t* accepted, void* stream) {
+    const Entry at{"rvm_stretch_accept"};
     if (n_s0 == 0) return 0;
-    if (n_params < 1 || n_s0 < 0 || !x || !lnp || !q || !lnp_new || !z)
-        return fail(-1, "rvm_stretch_accept: bad arguments");
-    hipError_t e = rvm::launch_stretch_accept(n_params, n_s0, s0_begin, x, lnp, q, lnp_new, z, seed, iteration, half,
-                                              draws, accepted, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_stretch_accept");
+    if (n_params < 1 || n_s0 < 0 || !x || !lnp || !q || !lnp_new || !z) return at.bad("bad arguments");
+    return at.done(rvm::launch_stretch_accept(n_params, n_s0, s0_begin, x, lnp, q, lnp_new, z, seed, iteration, half,
+                                              draws, accepted, (hipStream_t)stream));
 }
 
 // the scalar arguments the three parallel-tempering entry points share (null on success); `cols` =
@@ -259,57 +259,54 @@ static const char* pt_bad_shape(int32_t n_params, int32_t n_temps, int32_t n_hal
 int rvm_pt_stretch_propose(int32_t n_params, int32_t n_temps, int32_t n_half, const double* x, const double* c,
                            double a, uint64_t seed, uint64_t iteration, uint32_t half, const double* draws,
                            double* q_out, double* z_out, void* stream) {
-    if (const char* m = pt_bad_shape(n_params, n_temps, n_half, n_half))
-        return fail(-1, std::string("rvm_pt_stretch_propose: ") + m);
-    if (half > 1u) return fail(-1, "rvm_pt_stretch_propose: half must be 0 or 1");
-    if (!(a > 1.0)) return fail(-1, "rvm_pt_stretch_propose: stretch scale a must be > 1");
-    if (!x || !c || !q_out || !z_out) return fail(-1, "rvm_pt_stretch_propose: null x, c, q_out or z_out");
-    hipError_t e = rvm::launch_pt_stretch_propose(n_params, n_temps, n_half, x, c, a, seed, iteration, half, draws,
-                                                  q_out, z_out, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_pt_stretch_propose");
+    const Entry at{"rvm_pt_stretch_propose"};
+    if (const char* m = pt_bad_shape(n_params, n_temps, n_half, n_half)) return at.bad(m);
+    if (half > 1u) return at.bad("half must be 0 or 1");
+    if (const char* m = bad_scale(a)) return at.bad(m);
+    if (!x || !c || !q_out || !z_out) return at.null("x, c, q_out or z_out");
+    return at.done(rvm::launch_pt_stretch_propose(n_params, n_temps, n_half, x, c, a, seed, iteration, half, draws,
+                                                  q_out, z_out, (hipStream_t)stream));
 }
 
 int rvm_pt_stretch_accept(int32_t n_params, int32_t n_temps, int32_t n_half, const double* betas, double* x,
                           double* lnp, const double* q, const double* lnp_new, const double* z, uint64_t seed,
                           uint64_t iteration, uint32_t half, const double* draws, int32_t* accepted, void* stream) {
-    if (const char* m = pt_bad_shape(n_params, n_temps, n_half, n_half))
-        return fail(-1, std::string("rvm_pt_stretch_accept: ") + m);
-    if (half > 1u) return fail(-1, "rvm_pt_stretch_accept: half must be 0 or 1");
-    if (!betas) return fail(-1, "rvm_pt_stretch_accept: null betas");
-    if (!x || !lnp || !q || !lnp_new || !z) return fail(-1, "rvm_pt_stretch_accept: null x, lnp, q, lnp_new or z");
-    hipError_t e = rvm::launch_pt_stretch_accept(n_params, n_temps, n_half, betas, x, lnp, q, lnp_new, z, seed,
-                                                 iteration, half, draws, accepted, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_pt_stretch_accept");
+    const Entry at{"rvm_pt_stretch_accept"};
+    if (const char* m = pt_bad_shape(n_params, n_temps, n_half, n_half)) return at.bad(m);
+    if (half > 1u) return at.bad("half must be 0 or 1");
+    if (!betas) return at.null("betas");
+    if (!x || !lnp || !q || !lnp_new || !z) return at.null("x, lnp, q, lnp_new or z");
+    return at.done(rvm::launch_pt_stretch_accept(n_params, n_temps, n_half, betas, x, lnp, q, lnp_new, z, seed,
+                                                 iteration, half, draws, accepted, (hipStream_t)stream));
 }
 
 int rvm_pt_swap(int32_t n_params, int32_t n_temps, int32_t n_half, const double* betas, double* x0, double* x1,
                 double* lnp0, double* lnp1, uint64_t seed, uint64_t iteration, const double* draws,
                 int32_t* swapped, void* stream) {
-    if (const char* m = pt_bad_shape(n_params, n_temps, n_half, 2 * (int64_t)n_half))
-        return fail(-1, std::string("rvm_pt_swap: ") + m);
+    const Entry at{"rvm_pt_swap"};
+    if (const char* m = pt_bad_shape(n_params, n_temps, n_half, 2 * (int64_t)n_half)) return at.bad(m);
     if (n_temps == 1) return 0;  // one temperature has no neighbour: nothing to launch
-    if (!betas) return fail(-1, "rvm_pt_swap: null betas");
-    if (!x0 || !x1 || !lnp0 || !lnp1 || !swapped) return fail(-1, "rvm_pt_swap: null x0, x1, lnp0, lnp1 or swapped");
-    hipError_t e = rvm::launch_pt_swap(n_params, n_temps, n_half, betas, x0, x1, lnp0, lnp1, seed, iteration, draws,
-                                       swapped, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_pt_swap");
+    if (!betas) return at.null("betas");
+    if (!x0 || !x1 || !lnp0 || !lnp1 || !swapped) return at.null("x0, x1, lnp0, lnp1 or swapped");
+    return at.done(rvm::launch_pt_swap(n_params, n_temps, n_half, betas, x0, x1, lnp0, lnp1, seed, iteration, draws,
+                                       swapped, (hipStream_t)stream));
 }
 
 int rvm_pt_ladder_update(int32_t n_temps, int32_t n_half, const int32_t* swapped, const double* lnp0,
                          const double* lnp1, double kappa, double* betas, int64_t* swap_totals_prev,
                          double* ratios_out, int64_t* n_refused, double* lnp_moments, void* workspace,
                          void* stream) {
-    if (const char* m = pt_bad_shape(1, n_temps, n_half, 2 * (int64_t)n_half))
-        return fail(-1, std::string("rvm_pt_ladder_update: ") + m);
-    if (!std::isfinite(kappa) || kappa < 0.0) return fail(-1, "rvm_pt_ladder_update: kappa must be finite and >= 0");
+    const Entry at{"rvm_pt_ladder_update"};
+    if (const char* m = pt_bad_shape(1, n_temps, n_half, 2 * (int64_t)n_half)) return at.bad(m);
+    if (!std::isfinite(kappa) || kappa < 0.0) return at.bad("kappa must be finite and >= 0");
     if (n_temps == 1) return 0;  // one temperature has no ladder: nothing to launch
-    if (!swapped) return fail(-1, "rvm_pt_ladder_update: null swapped");
-    if (!lnp0 || !lnp1) return fail(-1, "rvm_pt_ladder_update: null lnp0 or lnp1");
-    if (!betas) return fail(-1, "rvm_pt_ladder_update: null betas");
-    if (!swap_totals_prev) return fail(-1, "rvm_pt_ladder_update: null swap_totals_prev");
-    if (!ratios_out) return fail(-1, "rvm_pt_ladder_update: null ratios_out");
-    if (!n_refused) return fail(-1, "rvm_pt_ladder_update: null n_refused");
-    if (!workspace) return fail(-1, "rvm_pt_ladder_update: null workspace");
+    if (!swapped) return at.null("swapped");
+    if (!lnp0 || !lnp1) return at.null("lnp0 or lnp1");
+    if (!betas) return at.null("betas");
+    if (!swap_totals_prev) return at.null("swap_totals_prev");
+    if (!ratios_out) return at.null("ratios_out");
+    if (!n_refused) return at.null("n_refused");
+    if (!workspace) return at.null("workspace");
     rvm::PtLadderArgs g;
     g.T = n_temps;
     g.Wh = n_half;
@@ -324,8 +321,7 @@ int rvm_pt_ladder_update(int32_t n_temps, int32_t n_half, const int32_t* swapped
     g.moments = lnp_moments;
     g.ws_totals = (int64_t*)workspace;
     g.ws_moments = (double*)workspace + (n_temps - 1);
-    hipError_t e = rvm::launch_pt_ladder_update(g, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_pt_ladder_update");
+    return at.done(rvm::launch_pt_ladder_update(g, (hipStream_t)stream));
 }
 
 // ---- the recorded chain (rvm_chain.hip) ----
@@ -339,33 +335,32 @@ static const char* chain_bad_shape(int32_t n_params, int32_t n_cols) {
 int rvm_chain_record(int32_t n_params, int32_t n_cols, const double* src, int64_t src_ld, int64_t src_col0,
                      int64_t col_stride, double* dst, int64_t dst_ld, int64_t dst_col0, const double* lnp_src,
                      double* lnp_dst, void* stream) {
-    if (const char* m = chain_bad_shape(n_params, n_cols)) return fail(-1, std::string("rvm_chain_record: ") + m);
-    if (!src) return fail(-1, "rvm_chain_record: null src");
-    if (!dst) return fail(-1, "rvm_chain_record: null dst");
-    if (col_stride < 1) return fail(-1, "rvm_chain_record: col_stride must be >= 1");
-    if (src_col0 < 0) return fail(-1, "rvm_chain_record: src_col0 must be >= 0");
-    if (dst_col0 < 0) return fail(-1, "rvm_chain_record: dst_col0 must be >= 0");
+    const Entry at{"rvm_chain_record"};
+    if (const char* m = chain_bad_shape(n_params, n_cols)) return at.bad(m);
+    if (!src) return at.null("src");
+    if (!dst) return at.null("dst");
+    if (col_stride < 1) return at.bad("col_stride must be >= 1");
+    if (src_col0 < 0) return at.bad("src_col0 must be >= 0");
+    if (dst_col0 < 0) return at.bad("dst_col0 must be >= 0");
     if (col_stride > (INT64_MAX - src_col0) / n_cols || src_ld < src_col0 + (int64_t)(n_cols - 1) * col_stride + 1)
-        return fail(-1, "rvm_chain_record: src_ld is smaller than the last gathered column + 1");
+        return at.bad("src_ld is smaller than the last gathered column + 1");
     if (dst_col0 > INT64_MAX - n_cols || dst_ld < dst_col0 + n_cols)
-        return fail(-1, "rvm_chain_record: dst_ld is smaller than dst_col0 + n_cols");
+        return at.bad("dst_ld is smaller than dst_col0 + n_cols");
     if ((lnp_src == nullptr) != (lnp_dst == nullptr))
-        return fail(-1, "rvm_chain_record: lnp_src and lnp_dst go together (both or neither)");
-    hipError_t e = rvm::launch_chain_record(n_params, n_cols, src, src_ld, src_col0, col_stride, dst, dst_ld, dst_col0,
-                                            lnp_src, lnp_dst, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_chain_record");
+        return at.bad("lnp_src and lnp_dst go together (both or neither)");
+    return at.done(rvm::launch_chain_record(n_params, n_cols, src, src_ld, src_col0, col_stride, dst, dst_ld, dst_col0,
+                                            lnp_src, lnp_dst, (hipStream_t)stream));
 }
 
 int rvm_chain_moments(const double* chain, int32_t n_params, int32_t n_cols, int64_t t0, int64_t t1, double* mean_out,
                       double* m2_out, void* stream) {
-    if (const char* m = chain_bad_shape(n_params, n_cols)) return fail(-1, std::string("rvm_chain_moments: ") + m);
-    if (!chain) return fail(-1, "rvm_chain_moments: null chain");
-    if (t0 < 0) return fail(-1, "rvm_chain_moments: t0 must be >= 0");
-    if (t1 <= t0) return fail(-1, "rvm_chain_moments: t1 must be > t0");
-    if (!mean_out) return fail(-1, "rvm_chain_moments: null mean_out");
-    if (!m2_out) return fail(-1, "rvm_chain_moments: null m2_out");
-    hipError_t e = rvm::launch_chain_moments(chain, n_params, n_cols, t0, t1, mean_out, m2_out, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_chain_moments");
+    const Entry at{"rvm_chain_moments"};
+    if (const char* m = chain_bad_shape(n_params, n_cols)) return at.bad(m);
+    if (!chain) return at.null("chain");
+    if (const char* m = bad_window(t0, t1)) return at.bad(m);
+    if (!mean_out) return at.null("mean_out");
+    if (!m2_out) return at.null("m2_out");
+    return at.done(rvm::launch_chain_moments(chain, n_params, n_cols, t0, t1, mean_out, m2_out, (hipStream_t)stream));
 }
 
 size_t rvm_chain_autocov_workspace_bytes(int32_t n_params, int32_t n_cols, int32_t n_lags) {
@@ -376,21 +371,19 @@ size_t rvm_chain_autocov_workspace_bytes(int32_t n_params, int32_t n_cols, int32
 
 int rvm_chain_autocov(const double* chain, const double* mean, int32_t n_params, int32_t n_cols, int64_t t0, int64_t t1,
                       int32_t lag0, int32_t n_lags, double* acov_out, void* workspace, void* stream) {
-    if (const char* m = chain_bad_shape(n_params, n_cols)) return fail(-1, std::string("rvm_chain_autocov: ") + m);
-    if (!chain) return fail(-1, "rvm_chain_autocov: null chain");
-    if (!mean) return fail(-1, "rvm_chain_autocov: null mean");
-    if (t0 < 0) return fail(-1, "rvm_chain_autocov: t0 must be >= 0");
-    if (t1 <= t0) return fail(-1, "rvm_chain_autocov: t1 must be > t0");
-    if (lag0 < 0) return fail(-1, "rvm_chain_autocov: lag0 must be >= 0");
-    if (n_lags < 1 || n_lags > (1 << 30)) return fail(-1, "rvm_chain_autocov: n_lags must be 1 .. 2^30");
-    if ((int64_t)lag0 + n_lags > t1 - t0)
-        return fail(-1, "rvm_chain_autocov: lag0 + n_lags - 1 must be at most t1 - t0 - 1");
-    if ((int64_t)n_params * n_lags > INT32_MAX) return fail(-1, "rvm_chain_autocov: n_params * n_lags beyond int32");
-    if (!acov_out) return fail(-1, "rvm_chain_autocov: null acov_out");
-    if (!workspace) return fail(-1, "rvm_chain_autocov: null workspace");
-    hipError_t e = rvm::launch_chain_autocov(chain, mean, n_params, n_cols, t0, t1, lag0, n_lags, acov_out,
-                                             (double*)workspace, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_chain_autocov");
+    const Entry at{"rvm_chain_autocov"};
+    if (const char* m = chain_bad_shape(n_params, n_cols)) return at.bad(m);
+    if (!chain) return at.null("chain");
+    if (!mean) return at.null("mean");
+    if (const char* m = bad_window(t0, t1)) return at.bad(m);
+    if (lag0 < 0) return at.bad("lag0 must be >= 0");
+    if (n_lags < 1 || n_lags > (1 << 30)) return at.bad("n_lags must be 1 .. 2^30");
+    if ((int64_t)lag0 + n_lags > t1 - t0) return at.bad("lag0 + n_lags - 1 must be at most t1 - t0 - 1");
+    if ((int64_t)n_params * n_lags > INT32_MAX) return at.bad("n_params * n_lags beyond int32");
+    if (!acov_out) return at.null("acov_out");
+    if (!workspace) return at.null("workspace");
+    return at.done(rvm::launch_chain_autocov(chain, mean, n_params, n_cols, t0, t1, lag0, n_lags, acov_out,
+                                             (double*)workspace, (hipStream_t)stream));
 }
 
 // ---- posterior summaries (rvm_summary.hip) ----
@@ -407,28 +400,28 @@ size_t rvm_rows_quantiles_workspace_bytes(int32_t n_rows, int32_t n_q) {
 int rvm_rows_quantiles(const double* x, int32_t n_rows, int64_t row_stride, int64_t n_outer, int64_t outer_stride,
                        int64_t n_inner, const double* q, int32_t n_q, double* out, int64_t* n_valid_out,
                        void* workspace, void* stream) {
-    if (!x) return fail(-1, "rvm_rows_quantiles: null x");
-    if (n_rows < 1 || n_rows > 65535) return fail(-1, "rvm_rows_quantiles: n_rows must be 1 .. 65535");
-    if (row_stride < 0) return fail(-1, "rvm_rows_quantiles: row_stride must be >= 0");
-    if (n_outer < 1) return fail(-1, "rvm_rows_quantiles: n_outer must be >= 1");
-    if (outer_stride < 0) return fail(-1, "rvm_rows_quantiles: outer_stride must be >= 0");
-    if (n_inner < 1) return fail(-1, "rvm_rows_quantiles: n_inner must be >= 1");
+    const Entry at{"rvm_rows_quantiles"};
+    if (!x) return at.null("x");
+    if (n_rows < 1 || n_rows > 65535) return at.bad("n_rows must be 1 .. 65535");
+    if (row_stride < 0) return at.bad("row_stride must be >= 0");
+    if (n_outer < 1) return at.bad("n_outer must be >= 1");
+    if (outer_stride < 0) return at.bad("outer_stride must be >= 0");
+    if (n_inner < 1) return at.bad("n_inner must be >= 1");
     if (n_outer > (int64_t)UINT32_MAX / n_inner)
-        return fail(-1, "rvm_rows_quantiles: n_outer * n_inner beyond the 2^32 - 1 elements a row's counters hold");
-    if (!q) return fail(-1, "rvm_rows_quantiles: null q");
-    if (n_q < 1 || n_q > RVM_MAX_QUANTILES) return fail(-1, "rvm_rows_quantiles: n_q must be 1 .. 16");
+        return at.bad("n_outer * n_inner beyond the 2^32 - 1 elements a row's counters hold");
+    if (!q) return at.null("q");
+    if (n_q < 1 || n_q > RVM_MAX_QUANTILES) return at.bad("n_q must be 1 .. 16");
     rvm::SelQ Q{};
     Q.n_q = n_q;
     for (int j = 0; j < n_q; j++) {
-        if (!(q[j] >= 0.0 && q[j] <= 1.0)) return fail(-1, "rvm_rows_quantiles: every q must lie in [0, 1]");
+        if (!(q[j] >= 0.0 && q[j] <= 1.0)) return at.bad("every q must lie in [0, 1]");
         Q.q[j] = q[j];
     }
-    if (!out) return fail(-1, "rvm_rows_quantiles: null out");
-    if (!workspace) return fail(-1, "rvm_rows_quantiles: null workspace");
-    if ((uintptr_t)workspace % 8 != 0) return fail(-1, "rvm_rows_quantiles: workspace must be 8-byte aligned");
-    hipError_t e = rvm::launch_rows_quantiles(x, n_rows, row_stride, n_outer, outer_stride, n_inner, Q, out, n_valid_out,
-                                              workspace, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_rows_quantiles");
+    if (!out) return at.null("out");
+    if (!workspace) return at.null("workspace");
+    if ((uintptr_t)workspace % 8 != 0) return at.bad("workspace must be 8-byte aligned");
+    return at.done(rvm::launch_rows_quantiles(x, n_rows, row_stride, n_outer, outer_stride, n_inner, Q, out, n_valid_out,
+                                              workspace, (hipStream_t)stream));
 }
 
 static const char* cov_bad_shape(int32_t n_params, int32_t n_cols) {
@@ -445,106 +438,116 @@ size_t rvm_chain_cov_workspace_bytes(int32_t n_params, int32_t n_cols) {
 
 int rvm_chain_cov(const double* chain, int32_t n_params, int32_t n_cols, int64_t t0, int64_t t1, const double* center,
                   double* cov_out, void* workspace, void* stream) {
-    if (const char* m = cov_bad_shape(n_params, n_cols)) return fail(-1, std::string("rvm_chain_cov: ") + m);
-    if (!chain) return fail(-1, "rvm_chain_cov: null chain");
-    if (t0 < 0) return fail(-1, "rvm_chain_cov: t0 must be >= 0");
-    if (t1 <= t0) return fail(-1, "rvm_chain_cov: t1 must be > t0");
-    if (!center) return fail(-1, "rvm_chain_cov: null center");
-    if (!cov_out) return fail(-1, "rvm_chain_cov: null cov_out");
-    if (!workspace) return fail(-1, "rvm_chain_cov: null workspace");
-    hipError_t e = rvm::launch_chain_cov(chain, n_params, n_cols, t0, t1, center, cov_out, (double*)workspace,
-                                         (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_chain_cov");
+    const Entry at{"rvm_chain_cov"};
+    if (const char* m = cov_bad_shape(n_params, n_cols)) return at.bad(m);
+    if (!chain) return at.null("chain");
+    if (const char* m = bad_window(t0, t1)) return at.bad(m);
+    if (!center) return at.null("center");
+    if (!cov_out) return at.null("cov_out");
+    if (!workspace) return at.null("workspace");
+    return at.done(rvm::launch_chain_cov(chain, n_params, n_cols, t0, t1, center, cov_out, (double*)workspace,
+                                         (hipStream_t)stream));
 }
 
 int rvm_chain_draw(const double* chain, int32_t n_params, int32_t n_cols, int64_t t0, int64_t t1, int32_t n_samples,
                    uint64_t seed, uint64_t draw_id, const double* draws, double* x_out, int64_t* idx_out,
                    void* stream) {
-    if (const char* m = chain_bad_shape(n_params, n_cols)) return fail(-1, std::string("rvm_chain_draw: ") + m);
-    if (!chain) return fail(-1, "rvm_chain_draw: null chain");
-    if (t0 < 0) return fail(-1, "rvm_chain_draw: t0 must be >= 0");
-    if (t1 <= t0) return fail(-1, "rvm_chain_draw: t1 must be > t0");
-    if (n_samples < 1) return fail(-1, "rvm_chain_draw: n_samples must be >= 1");
-    if (!x_out) return fail(-1, "rvm_chain_draw: null x_out");
-    hipError_t e = rvm::launch_chain_draw(chain, n_params, n_cols, t0, t1, n_samples, seed, draw_id, draws, x_out,
-                                          idx_out, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_chain_draw");
+    const Entry at{"rvm_chain_draw"};
+    if (const char* m = chain_bad_shape(n_params, n_cols)) return at.bad(m);
+    if (!chain) return at.null("chain");
+    if (const char* m = bad_window(t0, t1)) return at.bad(m);
+    if (n_samples < 1) return at.bad("n_samples must be >= 1");
+    if (!x_out) return at.null("x_out");
+    return at.done(rvm::launch_chain_draw(chain, n_params, n_cols, t0, t1, n_samples, seed, draw_id, draws, x_out,
+                                          idx_out, (hipStream_t)stream));
 }
 
 int rvm_mh_propose(int32_t n_params, int32_t n_chains, int64_t chain_begin, const double* x, const double* scales,
                    double step_size, uint64_t seed, uint64_t iteration, const double* draws, double* q_out,
                    void* stream) {
+    const Entry at{"rvm_mh_propose"};
     if (n_chains == 0) return 0;
-    if (n_params < 1 || n_chains < 0 || !x || !scales || !q_out) return fail(-1, "rvm_mh_propose: bad arguments");
-    hipError_t e = rvm::launch_mh_propose(n_params, n_chains, chain_begin, x, scales, step_size, seed, iteration, draws,
-                                          q_out, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_mh_propose");
+    if (n_params < 1 || n_chains < 0 || !x || !scales || !q_out) return at.bad("bad arguments");
+    return at.done(rvm::launch_mh_propose(n_params, n_chains, chain_begin, x, scales, step_size, seed, iteration, draws,
+                                          q_out, (hipStream_t)stream));
 }
 
 int rvm_mh_accept(int32_t n_params, int32_t n_chains, int64_t chain_begin, double* x, double* lnp, const double* q,
                   const double* lnp_new, uint64_t seed, uint64_t iteration, const double* draws, int32_t* accepted,
                   void* stream) {
+    const Entry at{"rvm_mh_accept"};
     if (n_chains == 0) return 0;
-    if (n_params < 1 || n_chains < 0 || !x || !lnp || !q || !lnp_new) return fail(-1, "rvm_mh_accept: bad arguments");
-    hipError_t e = rvm::launch_mh_accept(n_params, n_chains, chain_begin, x, lnp, q, lnp_new, seed, iteration, draws,
-                                         accepted, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_mh_accept");
+    if (n_params < 1 || n_chains < 0 || !x || !lnp || !q || !lnp_new) return at.bad("bad arguments");
+    return at.done(rvm::launch_mh_accept(n_params, n_chains, chain_begin, x, lnp, q, lnp_new, seed, iteration, draws,
+                                         accepted, (hipStream_t)stream));
 }
 
 int rvm_mh_step(const rvm_plan* plan, const rvm_param_map* map, int32_t n_params, int32_t n_chains,
                 int64_t chain_begin, double* x, double* lnp, const double* scales, double step_size, uint64_t seed,
                 uint64_t iteration, double hill_factor, double* lnp_new_out, int32_t* status_out, int32_t* accepted,
                 void* stream) {
-    if (!plan || !map) return fail(-1, "rvm_mh_step: null plan or map");
+    const Entry at{"rvm_mh_step"};
+    if (!plan || !map) return at.null("plan or map");
     if (n_chains == 0) return 0;
-    if (n_chains < 0 || n_chains > plan->max_walkers)
-        return fail(-1, "rvm_mh_step: n_chains exceeds the plan's max_walkers");
-    if (n_params < 1 || !x || !lnp || !scales) return fail(-1, "rvm_mh_step: bad arguments");
-    if (!(hill_factor >= 0.0)) return fail(-1, "rvm_mh_step: hill_factor must be >= 0");
+    if (n_chains < 0 || n_chains > plan->max_walkers) return at.bad("n_chains exceeds the plan's max_walkers");
+    if (n_params < 1 || !x || !lnp || !scales) return at.bad("bad arguments");
+    if (const char* m = bad_hill(hill_factor)) return at.bad(m);
     rvm::StretchArgs sa{};
-    if (const int rc = fill_map("rvm_mh_step", plan, map, n_params, &sa)) return rc;
-    sa.x = x;
-    sa.lnp = lnp;
-    sa.accepted = accepted;
-    sa.s0_begin = chain_begin;
-    sa.seed = seed;
-    sa.iteration = iteration;
-    sa.dim = n_params;
-    sa.xstride = n_chains;
+    if (const int rc = fill_map(at, plan, map, n_params, &sa)) return rc;
+    fill_stretch(&sa, n_params, n_chains, chain_begin, x, nullptr, lnp, 0, nullptr, 0.0, seed, iteration, 0, accepted);
     sa.mh_scale = scales;
     sa.mh_step = step_size;
-    hipError_t e = run_logl(plan, n_chains, nullptr, hill_factor, lnp_new_out, status_out, nullptr, sa, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_mh_step");
+    return at.done(run_logl(plan, n_chains, nullptr, hill_factor, lnp_new_out, status_out, nullptr, sa, (hipStream_t)stream));
+}
+
+static bool smala_cache_ok(const rvm_smala_cache* c) {
+    return c && c->lp && c->grad && c->mu && c->L && c->G && c->logdet && c->ok;
+}
+
+static rvm::SmalaCache smala_cache(const rvm_smala_cache* c) {
+    return rvm::SmalaCache{c->lp, c->grad, c->mu, c->L, c->G, c->logdet, c->ok};
+}
+
+// n_params free parameters of n_chains chains (every SMALA kernel; refused under "bad arguments")
+static bool smala_bad_shape(int32_t n_params, int32_t n_chains) {
+    return n_params < 1 || n_params > RVM_SMALA_MAX_PARAMS || n_chains < 0;
+}
+
+// the stencil a derive reads and its scalars (rvm_smala_derive's; refused under "bad arguments")
+static bool smala_bad_stencil(int32_t n_obs, const double* floor_, const double* lp_stencil,
+                              const int32_t* status_stencil, const double* rv_stencil, const double* inv_sigma2,
+                              double rel_step, double npoints_norm, double alpha) {
+    return n_obs < 0 || !floor_ || !lp_stencil || !status_stencil || (n_obs > 0 && (!rv_stencil || !inv_sigma2)) ||
+           !(rel_step > 0.0) || !(npoints_norm != 0.0) || !(alpha > 0.0);
 }
 
 int rvm_smala_stencil_logl(const rvm_plan* plan, const rvm_param_map* map, int32_t n_params, int32_t n_chains,
                            const double* x, double rel_step, const double* floor_, double hill_factor,
                            double* logl_out, int32_t* status_out, double* rv_out, void* stream) {
-    if (!plan || !map) return fail(-1, "rvm_smala_stencil_logl: null plan or map");
+    const Entry at{"rvm_smala_stencil_logl"};
+    if (!plan || !map) return at.null("plan or map");
     if (n_chains == 0) return 0;
     const int64_t W = (int64_t)(2 * n_params + 1) * n_chains;
     if (n_params < 1 || n_chains < 0 || !x || !floor_ || !logl_out || !status_out || !(rel_step > 0.0))
-        return fail(-1, "rvm_smala_stencil_logl: bad arguments");
-    if (W > plan->max_walkers) return fail(-1, "rvm_smala_stencil_logl: (2 n_params + 1) n_chains exceeds max_walkers");
-    if (!(hill_factor >= 0.0)) return fail(-1, "rvm_smala_stencil_logl: hill_factor must be >= 0");
+        return at.bad("bad arguments");
+    if (W > plan->max_walkers) return at.bad("(2 n_params + 1) n_chains exceeds max_walkers");
+    if (const char* m = bad_hill(hill_factor)) return at.bad(m);
     rvm::StretchArgs sa{};
-    if (const int rc = fill_map("rvm_smala_stencil_logl", plan, map, n_params, &sa)) return rc;
+    if (const int rc = fill_map(at, plan, map, n_params, &sa)) return rc;
     sa.dim = n_params;
     sa.fd_x = x;
     sa.fd_floor = floor_;
     sa.fd_rel = rel_step;
     sa.fd_n = n_chains;
-    hipError_t e = run_logl(plan, (int)W, nullptr, hill_factor, logl_out, status_out, rv_out, sa, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_smala_stencil_logl");
+    return at.done(run_logl(plan, (int)W, nullptr, hill_factor, logl_out, status_out, rv_out, sa, (hipStream_t)stream));
 }
 
 int rvm_fd_params(int32_t n_params, int32_t n_chains, const double* x, double rel_step, const double* floor_,
                   double* out, void* stream) {
+    const Entry at{"rvm_fd_params"};
     if (n_chains == 0) return 0;
-    if (n_params < 1 || n_chains < 0 || !x || !floor_ || !out || !(rel_step > 0.0))
-        return fail(-1, "rvm_fd_params: bad arguments");
-    hipError_t e = rvm::launch_fd_params(n_params, n_chains, x, rel_step, floor_, out, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_fd_params");
+    if (n_params < 1 || n_chains < 0 || !x || !floor_ || !out || !(rel_step > 0.0)) return at.bad("bad arguments");
+    return at.done(rvm::launch_fd_params(n_params, n_chains, x, rel_step, floor_, out, (hipStream_t)stream));
 }
 
 size_t rvm_logl_derivs_workspace_bytes(int32_t n_chains, int32_t n_dirs) {
@@ -556,55 +559,45 @@ size_t rvm_logl_derivs_workspace_bytes(int32_t n_chains, int32_t n_dirs) {
 int rvm_logl_derivs(const rvm_plan* plan, int32_t n_chains, const double* params, int32_t n_dirs,
                     const int32_t* dir_rows, double hill_factor, double* logl_out, double* grad_out, double* hess_out,
                     int32_t* status_out, void* workspace, void* stream) {
-    if (!plan) return fail(-1, "rvm_logl_derivs: null plan");
+    const Entry at{"rvm_logl_derivs"};
+    if (!plan) return at.null("plan");
     if (n_chains == 0) return 0;
     const int rows = plan_rows(plan);
     if (n_chains < 0 || n_dirs < 1 || n_dirs > rows || !dir_rows || !params || !grad_out || !hess_out || !workspace)
-        return fail(-1, "rvm_logl_derivs: bad arguments");
-    if ((size_t)n_chains * (size_t)(n_dirs * (n_dirs + 1) / 2) > (size_t)(1 << 30))
-        return fail(-1, "rvm_logl_derivs: too many chains x parameter pairs");
-    if (!(hill_factor >= 0.0)) return fail(-1, "rvm_logl_derivs: hill_factor must be >= 0");
-    for (int k = 0; k < n_dirs; k++) {
-        if (dir_rows[k] < 0 || dir_rows[k] >= rows) return fail(-1, "rvm_logl_derivs: dir_rows entry out of range");
-        for (int q = 0; q < k; q++)
-            if (dir_rows[q] == dir_rows[k]) return fail(-1, "rvm_logl_derivs: dir_rows entries must be distinct");
-    }
+        return at.bad("bad arguments");
     const size_t items = (size_t)n_chains * (size_t)(n_dirs * (n_dirs + 1) / 2);
+    if (items > (size_t)(1 << 30)) return at.bad("too many chains x parameter pairs");
+    if (const char* m = bad_hill(hill_factor)) return at.bad(m);
+    for (int k = 0; k < n_dirs; k++) {
+        if (dir_rows[k] < 0 || dir_rows[k] >= rows) return at.bad("dir_rows entry out of range");
+        for (int q = 0; q < k; q++)
+            if (dir_rows[q] == dir_rows[k]) return at.bad("dir_rows entries must be distinct");
+    }
     double* ws = reinterpret_cast<double*>(workspace);
     int32_t* wst = reinterpret_cast<int32_t*>(ws + 2 * 4 * items);
-    hipError_t e = rvm::launch_derivs(plan->dev, n_chains, params, n_dirs, dir_rows, hill_factor, ws, wst, logl_out,
-                                      grad_out, hess_out, status_out, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_logl_derivs");
+    return at.done(rvm::launch_derivs(plan->dev, n_chains, params, n_dirs, dir_rows, hill_factor, ws, wst, logl_out,
+                                      grad_out, hess_out, status_out, (hipStream_t)stream));
 }
 
-static bool smala_cache_ok(const rvm_smala_cache* c) {
-    return c && c->lp && c->grad && c->mu && c->L && c->G && c->logdet && c->ok;
-}
-
-static rvm::SmalaCache smala_cache(const rvm_smala_cache* c) {
-    return rvm::SmalaCache{c->lp, c->grad, c->mu, c->L, c->G, c->logdet, c->ok};
-}
-
-static int smala_derive(const char* who, int sides, int32_t n_params, int32_t n_chains, int32_t n_obs, const double* x,
+static int smala_derive(const Entry& at, int sides, int32_t n_params, int32_t n_chains, int32_t n_obs, const double* x,
                         double rel_step, const double* floor_, const double* lp_stencil,
                         const int32_t* status_stencil, const double* rv_stencil, const double* inv_sigma2,
                         double npoints_norm, double alpha, double eps, const rvm_smala_cache* out, void* stream) {
     if (n_chains == 0) return 0;
-    if (n_params < 1 || n_params > RVM_SMALA_MAX_PARAMS || n_chains < 0 || n_obs < 0 || !x || !floor_ ||
-        !lp_stencil || !status_stencil || (n_obs > 0 && (!rv_stencil || !inv_sigma2)) || !smala_cache_ok(out) ||
-        !(rel_step > 0.0) || !(npoints_norm != 0.0) || !(alpha > 0.0))
-        return fail(-1, std::string(who) + ": bad arguments");
-    hipError_t e = rvm::launch_smala_derive(n_params, n_chains, n_obs, x, rel_step, floor_, lp_stencil,
-                                            status_stencil, rv_stencil, inv_sigma2, npoints_norm, alpha, eps,
-                                            smala_cache(out), sides, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, who);
+    if (smala_bad_shape(n_params, n_chains) || !x || !smala_cache_ok(out) ||
+        smala_bad_stencil(n_obs, floor_, lp_stencil, status_stencil, rv_stencil, inv_sigma2, rel_step, npoints_norm,
+                          alpha))
+        return at.bad("bad arguments");
+    return at.done(rvm::launch_smala_derive(n_params, n_chains, n_obs, x, rel_step, floor_, lp_stencil, status_stencil,
+                                            rv_stencil, inv_sigma2, npoints_norm, alpha, eps, smala_cache(out), sides,
+                                            (hipStream_t)stream));
 }
 
 int rvm_smala_derive(int32_t n_params, int32_t n_chains, int32_t n_obs, const double* x, double rel_step,
                      const double* floor_, const double* lp_stencil, const int32_t* status_stencil,
                      const double* rv_stencil, const double* inv_sigma2, double npoints_norm, double alpha,
                      double eps, const rvm_smala_cache* out, void* stream) {
-    return smala_derive("rvm_smala_derive", 0, n_params, n_chains, n_obs, x, rel_step, floor_, lp_stencil,
+    return smala_derive({"rvm_smala_derive"}, 0, n_params, n_chains, n_obs, x, rel_step, floor_, lp_stencil,
                         status_stencil, rv_stencil, inv_sigma2, npoints_norm, alpha, eps, out, stream);
 }
 
@@ -612,7 +605,7 @@ int rvm_smala_derive_sides(int32_t n_params, int32_t n_chains, int32_t n_obs, co
                            const double* floor_, const double* lp_stencil, const int32_t* status_stencil,
                            const double* rv_stencil, const double* inv_sigma2, double npoints_norm, double alpha,
                            double eps, const rvm_smala_cache* out, void* stream) {
-    return smala_derive("rvm_smala_derive_sides", 1, n_params, n_chains, n_obs, x, rel_step, floor_, lp_stencil,
+    return smala_derive({"rvm_smala_derive_sides"}, 1, n_params, n_chains, n_obs, x, rel_step, floor_, lp_stencil,
                         status_stencil, rv_stencil, inv_sigma2, npoints_norm, alpha, eps, out, stream);
 }
 
@@ -620,26 +613,26 @@ int rvm_smala_center_accept(int32_t n_params, int32_t n_chains, int64_t chain_be
                             const double* lp_center, const int32_t* status_center, const rvm_smala_cache* cur,
                             const rvm_smala_cache* prop, double eps, uint64_t seed, uint64_t iteration,
                             const double* draws, int32_t* accepted, int32_t* failures, void* stream) {
+    const Entry at{"rvm_smala_center_accept"};
     if (n_chains == 0) return 0;
-    if (n_params < 1 || n_params > RVM_SMALA_MAX_PARAMS || n_chains < 0 || !x || !x_prop || !lp_center ||
-        !status_center || !smala_cache_ok(cur) || !smala_cache_ok(prop))
-        return fail(-1, "rvm_smala_center_accept: bad arguments");
-    hipError_t e = rvm::launch_smala_center_accept(n_params, n_chains, chain_begin, x, smala_cache(cur), x_prop,
+    if (smala_bad_shape(n_params, n_chains) || !x || !x_prop || !lp_center || !status_center || !smala_cache_ok(cur) ||
+        !smala_cache_ok(prop))
+        return at.bad("bad arguments");
+    return at.done(rvm::launch_smala_center_accept(n_params, n_chains, chain_begin, x, smala_cache(cur), x_prop,
                                                    smala_cache(prop), lp_center, status_center, eps, seed, iteration,
-                                                   draws, accepted, failures, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_smala_center_accept");
+                                                   draws, accepted, failures, (hipStream_t)stream));
 }
 
 int rvm_smala_metric(int32_t n_params, int32_t n_chains, const double* x, const double* lp, const int32_t* status,
                      const double* grad, const double* hess, double alpha, double eps, const rvm_smala_cache* out,
                      void* stream) {
+    const Entry at{"rvm_smala_metric"};
     if (n_chains == 0) return 0;
-    if (n_params < 1 || n_params > RVM_SMALA_MAX_PARAMS || n_chains < 0 || !x || !lp || !status || !grad || !hess ||
-        !smala_cache_ok(out) || !(alpha > 0.0))
-        return fail(-1, "rvm_smala_metric: bad arguments");
-    hipError_t e = rvm::launch_smala_metric(n_params, n_chains, x, lp, status, grad, hess, alpha, eps, smala_cache(out),
-                                            (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_smala_metric");
+    if (smala_bad_shape(n_params, n_chains) || !x || !lp || !status || !grad || !hess || !smala_cache_ok(out) ||
+        !(alpha > 0.0))
+        return at.bad("bad arguments");
+    return at.done(rvm::launch_smala_metric(n_params, n_chains, x, lp, status, grad, hess, alpha, eps, smala_cache(out),
+                                            (hipStream_t)stream));
 }
 
 int rvm_smala_derive_accept(int32_t n_params, int32_t n_chains, int64_t chain_begin, int32_t n_obs, double* x,
@@ -648,16 +641,16 @@ int rvm_smala_derive_accept(int32_t n_params, int32_t n_chains, int64_t chain_be
                             double npoints_norm, double alpha, double eps, const rvm_smala_cache* cur,
                             const rvm_smala_cache* prop, uint64_t seed, uint64_t iteration, const double* draws,
                             int32_t* accepted, int32_t* failures, void* stream) {
+    const Entry at{"rvm_smala_derive_accept"};
     if (n_chains == 0) return 0;
-    if (n_params < 1 || n_params > RVM_SMALA_MAX_PARAMS || n_chains < 0 || n_obs < 0 || !x || !x_prop || !floor_ ||
-        !lp_stencil || !status_stencil || (n_obs > 0 && (!rv_stencil || !inv_sigma2)) || !smala_cache_ok(cur) ||
-        !smala_cache_ok(prop) || !(rel_step > 0.0) || !(npoints_norm != 0.0) || !(alpha > 0.0))
-        return fail(-1, "rvm_smala_derive_accept: bad arguments");
-    hipError_t e = rvm::launch_smala_derive_accept(n_params, n_chains, n_obs, x_prop, rel_step, floor_, lp_stencil,
+    if (smala_bad_shape(n_params, n_chains) || !x || !x_prop || !smala_cache_ok(cur) || !smala_cache_ok(prop) ||
+        smala_bad_stencil(n_obs, floor_, lp_stencil, status_stencil, rv_stencil, inv_sigma2, rel_step, npoints_norm,
+                          alpha))
+        return at.bad("bad arguments");
+    return at.done(rvm::launch_smala_derive_accept(n_params, n_chains, n_obs, x_prop, rel_step, floor_, lp_stencil,
                                                    status_stencil, rv_stencil, inv_sigma2, npoints_norm, alpha, eps,
                                                    smala_cache(prop), chain_begin, x, smala_cache(cur), seed,
-                                                   iteration, draws, accepted, failures, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_smala_derive_accept");
+                                                   iteration, draws, accepted, failures, (hipStream_t)stream));
 }
 
 int rvm_smala_metric_accept(int32_t n_params, int32_t n_chains, int64_t chain_begin, double* x, const double* x_prop,
@@ -665,38 +658,36 @@ int rvm_smala_metric_accept(int32_t n_params, int32_t n_chains, int64_t chain_be
                             double alpha, double eps, const rvm_smala_cache* cur, const rvm_smala_cache* prop,
                             uint64_t seed, uint64_t iteration, const double* draws, int32_t* accepted,
                             int32_t* failures, void* stream) {
+    const Entry at{"rvm_smala_metric_accept"};
     if (n_chains == 0) return 0;
-    if (n_params < 1 || n_params > RVM_SMALA_MAX_PARAMS || n_chains < 0 || !x || !x_prop || !lp || !status || !grad ||
-        !hess || !smala_cache_ok(cur) || !smala_cache_ok(prop) || !(alpha > 0.0))
-        return fail(-1, "rvm_smala_metric_accept: bad arguments");
-    hipError_t e = rvm::launch_smala_metric_accept(n_params, n_chains, x_prop, lp, status, grad, hess, alpha, eps,
+    if (smala_bad_shape(n_params, n_chains) || !x || !x_prop || !lp || !status || !grad || !hess ||
+        !smala_cache_ok(cur) || !smala_cache_ok(prop) || !(alpha > 0.0))
+        return at.bad("bad arguments");
+    return at.done(rvm::launch_smala_metric_accept(n_params, n_chains, x_prop, lp, status, grad, hess, alpha, eps,
                                                    smala_cache(prop), chain_begin, x, smala_cache(cur), seed,
-                                                   iteration, draws, accepted, failures, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_smala_metric_accept");
+                                                   iteration, draws, accepted, failures, (hipStream_t)stream));
 }
 
 int rvm_smala_propose(int32_t n_params, int32_t n_chains, int64_t chain_begin, const double* x,
                       const rvm_smala_cache* cur, double eps, uint64_t seed, uint64_t iteration,
                       const double* draws, double* x_prop, void* stream) {
+    const Entry at{"rvm_smala_propose"};
     if (n_chains == 0) return 0;
-    if (n_params < 1 || n_params > RVM_SMALA_MAX_PARAMS || n_chains < 0 || !x || !x_prop || !smala_cache_ok(cur))
-        return fail(-1, "rvm_smala_propose: bad arguments");
-    hipError_t e = rvm::launch_smala_propose(n_params, n_chains, chain_begin, x, smala_cache(cur), eps, seed, iteration,
-                                             draws, x_prop, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_smala_propose");
+    if (smala_bad_shape(n_params, n_chains) || !x || !x_prop || !smala_cache_ok(cur)) return at.bad("bad arguments");
+    return at.done(rvm::launch_smala_propose(n_params, n_chains, chain_begin, x, smala_cache(cur), eps, seed, iteration,
+                                             draws, x_prop, (hipStream_t)stream));
 }
 
 int rvm_smala_accept(int32_t n_params, int32_t n_chains, int64_t chain_begin, double* x, const rvm_smala_cache* cur,
                      const double* x_prop, const rvm_smala_cache* prop, double eps, uint64_t seed,
                      uint64_t iteration, const double* draws, int32_t* accepted, int32_t* failures, void* stream) {
+    const Entry at{"rvm_smala_accept"};
     if (n_chains == 0) return 0;
-    if (n_params < 1 || n_params > RVM_SMALA_MAX_PARAMS || n_chains < 0 || !x || !x_prop || !smala_cache_ok(cur) ||
-        !smala_cache_ok(prop))
-        return fail(-1, "rvm_smala_accept: bad arguments");
-    hipError_t e = rvm::launch_smala_accept(n_params, n_chains, chain_begin, x, smala_cache(cur), x_prop,
+    if (smala_bad_shape(n_params, n_chains) || !x || !x_prop || !smala_cache_ok(cur) || !smala_cache_ok(prop))
+        return at.bad("bad arguments");
+    return at.done(rvm::launch_smala_accept(n_params, n_chains, chain_begin, x, smala_cache(cur), x_prop,
                                             smala_cache(prop), eps, seed, iteration, draws, accepted, failures,
-                                            (hipStream_t)stream);
-    return e == hipSuccess ? 0 : hip_fail(e, "rvm_smala_accept");
+                                            (hipStream_t)stream));
 }
 
 }  // extern "C"

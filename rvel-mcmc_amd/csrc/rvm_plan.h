@@ -32,4 +32,13 @@ namespace rvm {
 // set rvm_last_error's message for this thread and return `code` (rvm_abi.hip)
 int fail(int code, const std::string& msg);
 int hip_fail(hipError_t e, const char* where);  // code -3, "<where>: <the runtime's message>"
+
+// An entry point's name, said once: its refusals (code -1, "<name>: <text>") and its HIP tail report
+// under it.  Nothing here builds a string unless the call fails.
+struct Entry {
+    const char* name;
+    int bad(const char* text) const { return fail(-1, std::string(name) + ": " + text); }
+    int null(const char* arg) const { return fail(-1, std::string(name) + ": null " + arg); }
+    int done(hipError_t e) const { return e == hipSuccess ? 0 : hip_fail(e, name); }
+};
 }  // namespace rvm

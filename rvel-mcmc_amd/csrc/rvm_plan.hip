@@ -10,6 +10,7 @@
 #include "rvm_plan.h"
 #include "rvm_plan_host.h"
 
+using rvm::Entry;
 using rvm::fail;
 using rvm::hip_fail;
 
@@ -223,18 +224,23 @@ int prepare_kernels(const rvm::DevPlan& P) {
     return 0;
 }
 
-// n words of DevPlan::hw from word `first` on (zeros on a plan without a hedge), zeroed after the read on request
-int read_hw_words(rvm_plan* plan, const char* who, int first, int n, int32_t reset, void* stream,
-                  unsigned long long* h) {
-    if (!plan) return fail(-1, std::string(who) + ": null plan");
-    std::memset(h, 0, n * sizeof(*h));
-    if (plan->dev.hw == nullptr) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    unsigned long long* d = plan->dev.hw + first;
-    hipError_t e = hipMemcpyAsync(h, d, n * sizeof(*h), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && reset) e = hipMemsetAsync(d, 0, n * sizeof(*h), st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return e == hipSuccess ? 0 : hip_fail(e, who);
+// The words of DevPlan::hw from word `first` on into the non-null pointers of `out` (zeros on a plan without
+// a hedge), zeroed after the read on request.  Nothing is written when the read fails.
+template <int N>
+int read_hw_words(const Entry& at, rvm_plan* plan, int first, int32_t reset, void* stream, int64_t* const (&out)[N]) {
+    if (!plan) return at.null("plan");
+    unsigned long long h[N] = {};
+    if (plan->dev.hw != nullptr) {
+        hipStream_t st = (hipStream_t)stream;
+        unsigned long long* d = plan->dev.hw + first;
+        hipError_t e = hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && reset) e = hipMemsetAsync(d, 0, sizeof(h), st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return at.done(e);
+    }
+    for (int i = 0; i < N; i++)
+        if (out[i]) *out[i] = (int64_t)h[i];
+    return 0;
 }
 
 }  // namespace
@@ -288,14 +294,15 @@ void rvm_plan_destroy(rvm_plan* plan) {
 }
 
 int rvm_plan_set_certain_reject(rvm_plan* plan, int32_t on) {
-    if (!plan) return fail(-1, "rvm_plan_set_certain_reject: null plan");
+    if (!plan) return Entry{"rvm_plan_set_certain_reject"}.null("plan");
     plan->dev.cut = on ? 1 : 0;
     return 0;
 }
 
 int rvm_plan_set_verify_eccentricity(rvm_plan* plan, double e) {
-    if (!plan) return fail(-1, "rvm_plan_set_verify_eccentricity: null plan");
-    if (std::isnan(e) || e >= 1.0) return fail(-1, "rvm_plan_set_verify_eccentricity: e must be < 1 (<= 0: off)");
+    const Entry at{"rvm_plan_set_verify_eccentricity"};
+    if (!plan) return at.null("plan");
+    if (std::isnan(e) || e >= 1.0) return at.bad("e must be < 1 (<= 0: off)");
     plan->dev.e2_guard = e > 0.0 ? e * e : INFINITY;
     {
         const char* cf = getenv("RVM_CUT_FACTOR");  // (A/B knob: the guard's factor)
@@ -309,19 +316,20 @@ int rvm_plan_set_verify_eccentricity(rvm_plan* plan, double e) {
 }
 
 int rvm_plan_extension(const rvm_plan* plan, int32_t* ext_mult) {
-    if (!plan) return fail(-1, "rvm_plan_extension: null plan");
+    if (!plan) return Entry{"rvm_plan_extension"}.null("plan");
     if (ext_mult) *ext_mult = plan->dev.ext_mult;
     return 0;
 }
 
 int rvm_plan_counters(rvm_plan* plan, int32_t reset, int64_t* out, int32_t n, void* stream) {
-    if (!plan) return fail(-1, "rvm_plan_counters: null plan");
-    if (n < 0 || (n > 0 && !out)) return fail(-1, "rvm_plan_counters: bad output array");
+    const Entry at{"rvm_plan_counters"};
+    if (!plan) return at.null("plan");
+    if (n < 0 || (n > 0 && !out)) return at.bad("bad output array");
     hipStream_t st = (hipStream_t)stream;
     unsigned long long h[RVM_N_COUNTERS] = {};
     hipError_t e = hipMemcpyAsync(h, plan->dev.counters, sizeof(h), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return hip_fail(e, "rvm_plan_counters");
+    if (e != hipSuccess) return at.done(e);
     for (int i = 0; i < n; i++) out[i] = i < RVM_N_COUNTERS ? (int64_t)h[i] : 0;
     if (reset) {
         // the hand-off slots back to their sentinels (late level-1 stores of a launch that gave up
@@ -336,38 +344,24 @@ int rvm_plan_counters(rvm_plan* plan, int32_t reset, int64_t* out, int32_t n, vo
 
 int rvm_plan_hedge_stats(rvm_plan* plan, int32_t reset, int64_t* hedged, int64_t* replayed, int64_t* missed,
                          void* stream) {
-    unsigned long long h[3];
-    const int rc = read_hw_words(plan, "rvm_plan_hedge_stats", rvm::RVM_HW_STATS, 3, reset, stream, h);
-    if (rc != 0) return rc;
-    if (hedged) *hedged = (int64_t)h[0];
-    if (replayed) *replayed = (int64_t)h[1];
-    if (missed) *missed = (int64_t)h[2];
-    return 0;
+    int64_t* const out[] = {hedged, replayed, missed};
+    return read_hw_words({"rvm_plan_hedge_stats"}, plan, rvm::RVM_HW_STATS, reset, stream, out);
 }
 
 int rvm_plan_hedge_marks(rvm_plan* plan, int32_t reset, int64_t* marked, int64_t* gave_up, void* stream) {
-    unsigned long long h[2];
-    const int rc = read_hw_words(plan, "rvm_plan_hedge_marks", rvm::RVM_HW_STATS + 3, 2, reset, stream, h);
-    if (rc != 0) return rc;
-    if (marked) *marked = (int64_t)h[0];
-    if (gave_up) *gave_up = (int64_t)h[1];
-    return 0;
+    int64_t* const out[] = {marked, gave_up};
+    return read_hw_words({"rvm_plan_hedge_marks"}, plan, rvm::RVM_HW_STATS + 3, reset, stream, out);
 }
 
 int rvm_plan_hedge_waits(rvm_plan* plan, int32_t reset, int64_t* waited, int64_t* late_hits, int64_t* gave_way,
                          void* stream) {
-    unsigned long long h[3];
-    const int rc = read_hw_words(plan, "rvm_plan_hedge_waits", rvm::RVM_HW_WAIT, 3, reset, stream, h);
-    if (rc != 0) return rc;
-    if (waited) *waited = (int64_t)h[0];
-    if (late_hits) *late_hits = (int64_t)h[1];
-    if (gave_way) *gave_way = (int64_t)h[2];
-    return 0;
+    int64_t* const out[] = {waited, late_hits, gave_way};
+    return read_hw_words({"rvm_plan_hedge_waits"}, plan, rvm::RVM_HW_WAIT, reset, stream, out);
 }
 
 int rvm_plan_faults(rvm_plan* plan, int32_t reset, int64_t* handoff_timeouts, int64_t* nonfinite,
                     int64_t* unresolved, int64_t* refined, int64_t* truncated, void* stream) {
-    if (!plan) return fail(-1, "rvm_plan_faults: null plan");
+    if (!plan) return Entry{"rvm_plan_faults"}.null("plan");
     int64_t c[RVM_N_COUNTERS] = {};
     const int rc = rvm_plan_counters(plan, reset, c, RVM_N_COUNTERS, stream);
     if (rc != 0) return rc;
@@ -380,8 +374,9 @@ int rvm_plan_faults(rvm_plan* plan, int32_t reset, int64_t* handoff_timeouts, in
 }
 
 int rvm_plan_time_kernels(rvm_plan* plan, int32_t max_launches) {
-    if (!plan) return fail(-1, "rvm_plan_time_kernels: null plan");
-    if (max_launches < 0 || max_launches > 4096) return fail(-1, "rvm_plan_time_kernels: max_launches out of range");
+    const Entry at{"rvm_plan_time_kernels"};
+    if (!plan) return at.null("plan");
+    if (max_launches < 0 || max_launches > 4096) return at.bad("max_launches out of range");
     while ((int32_t)plan->tev.size() < 3 * max_launches) {
         hipEvent_t ev;
         const hipError_t e = hipEventCreate(&ev);
@@ -394,14 +389,15 @@ int rvm_plan_time_kernels(rvm_plan* plan, int32_t max_launches) {
 }
 
 int rvm_plan_kernel_times(rvm_plan* plan, float* logl_ms, float* refine_ms, int32_t max, int32_t* n_out) {
-    if (!plan || max < 0) return fail(-1, "rvm_plan_kernel_times: bad arguments");
+    const Entry at{"rvm_plan_kernel_times"};
+    if (!plan || max < 0) return at.bad("bad arguments");
     const int n = std::min(plan->tn, max);
     for (int i = 0; i < n; i++) {
         hipError_t e = hipEventSynchronize(plan->tev[3 * i + 2]);
         float a = 0.0f, b = 0.0f;
         if (e == hipSuccess) e = hipEventElapsedTime(&a, plan->tev[3 * i], plan->tev[3 * i + 1]);
         if (e == hipSuccess) e = hipEventElapsedTime(&b, plan->tev[3 * i + 1], plan->tev[3 * i + 2]);
-        if (e != hipSuccess) return hip_fail(e, "rvm_plan_kernel_times");
+        if (e != hipSuccess) return at.done(e);
         if (logl_ms) logl_ms[i] = a;
         if (refine_ms) refine_ms[i] = b;
     }
@@ -412,8 +408,9 @@ int rvm_plan_kernel_times(rvm_plan* plan, float* logl_ms, float* refine_ms, int3
 }
 
 int rvm_plan_set_handoff_timeout(rvm_plan* plan, double seconds) {
-    if (!plan) return fail(-1, "rvm_plan_set_handoff_timeout: null plan");
-    if (!(seconds > 0.0) || !(seconds < 1e9)) return fail(-1, "rvm_plan_set_handoff_timeout: seconds out of range");
+    const Entry at{"rvm_plan_set_handoff_timeout"};
+    if (!plan) return at.null("plan");
+    if (!(seconds > 0.0) || !(seconds < 1e9)) return at.bad("seconds out of range");
     const double ticks = seconds * 1e8;  // 100 MHz real-time counter
     plan->dev.spin_ticks = ticks < 1.0 ? 1ull : (unsigned long long)ticks;
     plan->dev.hedge_wait_ticks = rvm::hedge_wait_bound(plan->dev.spin_ticks);
@@ -421,7 +418,7 @@ int rvm_plan_set_handoff_timeout(rvm_plan* plan, double seconds) {
 }
 
 int rvm_plan_info(const rvm_plan* plan, int32_t* sf, int32_t* sb, int32_t* ef, int32_t* eb) {
-    if (!plan) return fail(-1, "rvm_plan_info: null plan");
+    if (!plan) return Entry{"rvm_plan_info"}.null("plan");
     if (sf) *sf = plan->steps[0];
     if (sb) *sb = plan->steps[1];
     if (ef) *ef = plan->dev.fwd.n_epochs;

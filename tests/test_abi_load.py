@@ -1,6 +1,7 @@
 """The C-ABI library loads on a CPU-only host and exports every symbol include/rvmcmc.h declares.
 
 No compute calls here (no GPU); the GPU tests exercise the same entry points."""
+import ctypes as C
 import os
 import re
 
@@ -9,10 +10,57 @@ from conftest import ROOT
 from rvmcmc import _lib
 
 
-def header_functions():
+def header_source():
+    """include/rvmcmc.h without its comments."""
     src = open(os.path.join(ROOT, "include", "rvmcmc.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(rvm_[a-z_0-9]+)\s*\(", src)))
+    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+
+
+def header_functions():
+    return sorted(set(re.findall(r"\b(rvm_[a-z_0-9]+)\s*\(", header_source())))
+
+
+def header_prototypes():
+    """{name: (return type, [(argument type, argument name), ...])} of every prototype the header declares;
+    a type is its C spelling without `const` and without blanks (`double*`, `rvm_plan**`, `int32_t`)."""
+    out = {}
+    for ret, name, args in re.findall(r"^(int|void|size_t|const char\*)\s+(rvm_\w+)\s*\(([^)]*)\)\s*;",
+                                      header_source(), flags=re.M):
+        out[name] = (ret, [])
+        for a in args.split(","):
+            m = re.match(r"(.*?)(\w+)$", " ".join(a.split()))
+            if m.group(0) != "void":
+                out[name][1].append((m.group(1).replace("const ", "").replace(" ", ""), m.group(2)))
+    return out
+
+
+def header_defines():
+    """{name: value} of the header's RVM_* constants (an expression over earlier ones evaluated)."""
+    out = {}
+    for name, text in re.findall(r"^#define\s+(RVM_\w+)\s+(.+?)\s*$", header_source(), flags=re.M):
+        out[name] = eval(re.sub(r"(\d)ull\b", r"\1", text), {"__builtins__": {}}, dict(out))
+    return out
+
+
+SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32,
+           "uint64_t": C.c_uint64, "double": C.c_double, "float": C.c_float, "size_t": C.c_size_t, "void": None,
+           "const char*": C.c_char_p}
+STRUCTS = {"rvm_config": _lib.RvmConfig, "rvm_param_map": _lib.ParamMapC, "rvm_smala_cache": _lib.SmalaCache}
+
+
+def allowed_ctypes(ctype):
+    """The ctypes a C type of the header may be mirrored as (the rule of DESIGN.md section 10 item 13)."""
+    if ctype in SCALARS:
+        return (SCALARS[ctype],)
+    if ctype in ("rvm_plan*", "void*"):
+        return (C.c_void_p,)
+    if ctype == "rvm_plan**":
+        return (C.POINTER(C.c_void_p),)
+    assert ctype.endswith("*") and not ctype.endswith("**"), ctype
+    if ctype[:-1] in STRUCTS:
+        return (C.POINTER(STRUCTS[ctype[:-1]]),)
+    # any other data pointer: a device address, or a host array of the element type
+    return (C.c_void_p, C.POINTER(SCALARS[ctype[:-1]]))
 
 
 def test_header_declares_expected_surface():
@@ -29,11 +77,32 @@ def test_library_exports_every_header_symbol():
     lib = _lib.load()
     for f in header_functions():
         assert hasattr(lib, f), f"librvmcmc.so lacks {f}"
-    assert lib.rvm_abi_version() == _lib.ABI_VERSION == 12
+    assert lib.rvm_abi_version() == _lib.ABI_VERSION == header_defines()["RVM_ABI_VERSION"]
 
 
 def test_python_binding_matches_header():
-    assert set(_lib.SIGNATURES) == set(header_functions())
+    """Every prototype of the header against its ctypes mirror: return type, arity, each argument's type."""
+    protos = header_prototypes()
+    assert set(protos) == set(header_functions())  # (the prototype parser missed none)
+    assert set(_lib.SIGNATURES) == set(protos)
+    for name, (ret, args) in protos.items():
+        res, argtypes = _lib.SIGNATURES[name]
+        assert res is SCALARS[ret], f"{name}: returns {ret}, mirrored as {res}"
+        assert len(argtypes) == len(args), f"{name}: {len(args)} arguments, {len(argtypes)} mirrored"
+        for i, ((ctype, arg), got) in enumerate(zip(args, argtypes)):
+            ok = any(got is t for t in allowed_ctypes(ctype))
+            assert ok, f"{name}: argument {i} ({ctype} {arg}) mirrored as {got}"
+
+
+def test_python_constants_match_header():
+    """Every RVM_* constant _lib.py defines, and ABI_VERSION, is the header's #define (RVM_MAX_PARAM_ROWS:
+    the header's expression, evaluated)."""
+    defines = header_defines()
+    mirrored = {k: v for k, v in vars(_lib).items() if k.startswith("RVM_") and isinstance(v, int)}
+    assert len(mirrored) >= 11 and set(mirrored) <= set(defines), set(mirrored) - set(defines)
+    for k, v in mirrored.items():
+        assert v == defines[k], (k, v, defines[k])
+    assert _lib.ABI_VERSION == defines["RVM_ABI_VERSION"]
 
 
 def test_argument_errors_do_not_touch_the_device():
