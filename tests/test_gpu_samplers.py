@@ -142,12 +142,25 @@ def test_ensemble_reproducible_and_moves():
     assert np.isfinite(runs[0][1]).all()
 
 
-@pytest.mark.parametrize("case", ["s2", "s2_fixed_params", "s2_wide", "s2_two_groups", "three_planets"])
+def _large_system(case):
+    """Systems of more than 16 free parameters (the stretch kernels' dim > 16 paths): four planar planets, 20; three
+    inclined ones, 21."""
+    from test_gpu_logl import EXTRA_PLANETS
+
+    planets = [dict(p) for p in S2_PLANETS + EXTRA_PLANETS]
+    if case == "three_inclined":
+        planets = [dict(p, ix=0.03 * (i + 1), iy=-0.02 * i) for i, p in enumerate(planets[:3])]
+    return planets
+
+
+@pytest.mark.parametrize("case", ["s2", "s2_fixed_params", "s2_wide", "s2_two_groups", "three_planets", "four_planets",
+                                  "three_inclined"])
 def test_fused_half_step_matches_three_launch_path(case):
     """rvm_stretch_half_step (propose + logL + accept in one launch) against the separate
     propose / logl / accept launches with the same Philox draws: positions, lnp and accept counts
     bit-identical after several iterations.  Covers fixed (non-free) kernel rows, prior /
-    encounter proposals (wide ball), two walker groups per block (large halves) and 3 planets."""
+    encounter proposals (wide ball), two walker groups per block (large halves), 3 planets, and 20 and 21 free
+    parameters (4 planets; 3 inclined ones)."""
     torch = _torch()
     from rvmcmc import state
     from rvmcmc.ensemble import EnsembleSampler
@@ -163,10 +176,13 @@ def test_fused_half_step_matches_three_launch_path(case):
         W, iters = 2 * 8256, 2
     elif case == "three_planets":
         planets.append({"m": 1e-3, "a": 2.6, "h": 0.05, "k": 0.0, "l": 1.0})
+    elif case in ("four_planets", "three_inclined"):
+        planets = _large_system(case)
     s = state.State(planets=planets, **kw)
+    assert case not in ("four_planets", "three_inclined") or s.Nvars > 16
     obs = s2_obs_oracle()
     rng = np.random.default_rng(3)
-    scales = np.array([S2_SCALES[k] for k in s.get_rawkeys()])
+    scales = np.array([S2_SCALES.get(k, 0.05) for k in s.get_rawkeys()])
     X0 = s.get_params()[None] + rel * scales * rng.standard_normal((W, s.Nvars))
     runs = []
     for fused in (True, False):
@@ -189,13 +205,16 @@ def test_fused_half_step_matches_three_launch_path(case):
 
 
 @pytest.mark.parametrize("case", ["s2", "s2_fixed_params", "s2_wide", "one_planet", "three_planets", "inclined",
-                                  "s2_large", "s2_config2", "s2_bench_shape", "s2_bench_shape_wide"])
+                                  "s2_large", "s2_config2", "s2_bench_shape", "s2_bench_shape_wide", "four_planets",
+                                  "three_inclined"])
 def test_speculative_iteration_matches_half_steps(case):
     """rvm_stretch_iteration_begin / _end (both half-steps from one launch of 3 n walker slots,
     half 1 evaluated against both possible positions of its partner) against two fused half-step
     launches: positions, lnp, accept counts and the mirrors bit-identical after several
     iterations.  Covers fixed kernel rows, prior / encounter proposals, 1 / 2 / 3 planets (1, 2 and
-    4 lanes per walker), inclined orbits and a batch whose 3 n slots need two-group blocks."""
+    4 lanes per walker), inclined orbits, a batch whose 3 n slots need two-group blocks, and 20 and 21 free
+    parameters (4 planets; 3 inclined ones: the end kernel's dim > 16 instantiation and the 4-lane fused prologue
+    at that many staged rows)."""
     torch = _torch()
     from rvmcmc import state
     from rvmcmc.ensemble import EnsembleSampler
@@ -222,7 +241,10 @@ def test_speculative_iteration_matches_half_steps(case):
         W, iters = 4096, 3
     elif case == "s2_bench_shape_wide":  # the same under uneven load: redone segments, prior / encounter exits
         W, iters, rel = 4096, 3, 0.1
+    elif case in ("four_planets", "three_inclined"):
+        planets = _large_system(case)
     s = state.State(planets=planets, **kw)
+    assert case not in ("four_planets", "three_inclined") or s.Nvars > 16
     obs = s2_obs_oracle()
     rng = np.random.default_rng(5)
     scales = np.array([S2_SCALES.get(k, 0.05) for k in s.get_rawkeys()])

@@ -1,8 +1,8 @@
 """The likelihood launch's layout, on the host (rvm_plan_host.cpp choose_logl_layout, rvm_internal.h LoglLds; no
 GPU): over a grid of plans and launch sizes the dynamic-LDS request is LoglLds's total, that total is the sum
 the layouts' comments state, every range of it lies inside without overlap, and the choice keeps its
-invariants; and the layout of every shape the GPU tests name (tests/test_gpu_logl.py) is pinned, each value
-derived from the rule.  rvm_plan_host.cpp is built with the host compiler and a small driver, as
+invariants; and the layout of every shape the GPU tests name (tests/test_gpu_logl.py, and the adaptive plans of
+tests/test_gpu_resolve_systems.py) is pinned, each value derived from the rule.  rvm_plan_host.cpp is built with the host compiler and a small driver, as
 tests/test_hedge_wait_host_cpu.py does."""
 import json
 import os
@@ -120,6 +120,18 @@ int main() {
         std::printf("%s\"%d:%d\": [%d, %d, %d, %d, %d, %d, %d, %u, %u, %u]", i ? ", " : "", pins[i][0], pins[i][1], Y.G, Y.cx,
                     Y.nA, Y.nB, Y.tB, Y.splitA, Y.lsx, Y.grid_x, Y.grid_y, Y.block);
     }
+    // the adaptive GPU tests' shapes (tests/test_gpu_resolve_systems.py): plans with the extension and resolve_max 4,
+    // otherwise as above; plain launches (not fused) that ask for no model RVs; {planets, inclined, W}
+    const int apins[19][3] = {{3, 0, 24}, {3, 0, 256}, {3, 0, 2304}, {3, 0, 3264}, {3, 0, 3265},
+                              {4, 0, 24}, {4, 0, 256}, {4, 0, 2304},
+                              {2, 1, 24}, {2, 1, 256}, {2, 1, 2304}, {2, 1, 4096}, {2, 1, 4097},
+                              {3, 1, 24}, {3, 1, 256}, {3, 1, 2304}, {4, 1, 24}, {4, 1, 256}, {4, 1, 2304}};
+    for (int i = 0; i < 19; i++) {
+        const DevPlan P = plan(apins[i][0], apins[i][1], 4, lad4, 51, 4, 1, 256, apins[i][2]);
+        const LoglLayout Y = choose_logl_layout(P, apins[i][2], false, false, true, BUD_LC, BUD_LS);
+        std::printf(", \"%s%d:%d\": [%d, %d, %d, %d, %d, %d, %d, %u, %u, %u]", apins[i][1] ? "i" : "p", apins[i][0],
+                    apins[i][2], Y.G, Y.cx, Y.nA, Y.nB, Y.tB, Y.splitA, Y.lsx, Y.grid_x, Y.grid_y, Y.block);
+    }
     std::printf("}}\n");
     return 0;
 }
@@ -191,6 +203,46 @@ PINS = {
     # 4160: 260 groups; tB = 8, nb = 65, 325 > 256: two groups per block, grid 130 x 2 of 8 waves
     "3:4160": [2, 0, 0, 0, 8, 0, 0, 130, 2, 512],
 }
+
+# The shapes tests/test_gpu_resolve_systems.py names ("p" planar / "i" inclined, planets : W): adaptive plans
+# (resolve_max 4, so the extension level m4 = 8 and the t = 0 state in LDS), max_walkers = W, plain launches
+# without model RVs.  The extension runs beside the main pass (xcon) as a fifth wave of one-group blocks (cx) from
+# RVM_CX_MIN_WALKERS = 32 walkers on, or as a fifth level of the level-split layout (lsx, type-B blocks of 8
+# units) where two groups would share a block.  3 and 4 planets: 16 walkers per group; 2 planets: 32.
+PINS.update({
+    # 24: 2 groups (i2: 1), below RVM_CX_MIN_WALKERS: no cx, the extension after the main pass; 4 waves
+    "p3:24": [1, 0, 0, 0, 8, 0, 0, 2, 2, 256],
+    "p4:24": [1, 0, 0, 0, 8, 0, 0, 2, 2, 256],
+    "i2:24": [1, 0, 0, 0, 8, 0, 0, 1, 2, 256],
+    "i3:24": [1, 0, 0, 0, 8, 0, 0, 2, 2, 256],
+    "i4:24": [1, 0, 0, 0, 8, 0, 0, 2, 2, 256],
+    # 256: 16 groups (i2: 8), one per block with the extension wave: 5 waves
+    "p3:256": [1, 1, 0, 0, 8, 0, 0, 16, 2, 320],
+    "p4:256": [1, 1, 0, 0, 8, 0, 0, 16, 2, 320],
+    "i2:256": [1, 1, 0, 0, 8, 0, 0, 8, 2, 320],
+    "i3:256": [1, 1, 0, 0, 8, 0, 0, 16, 2, 320],
+    "i4:256": [1, 1, 0, 0, 8, 0, 0, 16, 2, 320],
+    # 2304: 144 groups, 288 > 256: crowded.  4 planets and inclined: two groups would share a block, so lsx with
+    # nb = ceil(288 / 8) = 36, 144 + 36 = 180 <= 256 blocks
+    "p4:2304": [2, 0, 144, 36, 8, 0, 1, 180, 1, 512],
+    "i3:2304": [2, 0, 144, 36, 8, 0, 1, 180, 1, 512],
+    "i4:2304": [2, 0, 144, 36, 8, 0, 1, 180, 1, 512],
+    # 3 planar planets pair one-group blocks (G = 1, cx) instead -- but the plan has the level-split workspace,
+    # and the fixed-resolution rule above then still applies: tB = 6 (144 + 48 = 192 <= 256), c_dec = 10 below
+    # c_cpl = m3 ceil(288 / 256) = 14: level-split without the fifth level (the extension after the main pass),
+    # 144 + 48 blocks.  (cx is the coupled layout's and unused here.)
+    "p3:2304": [1, 1, 144, 48, 6, 1, 0, 192, 1, 512],
+    # ... up to 204 groups (3264 walkers: tB = 8, 204 + 51 = 255 <= 256).  From 205 groups on (3265 walkers, the
+    # last group with one: 205 + 52 = 257 > 256) the level-split layout does not fit and the paired one-group blocks
+    # run: 205 x 2 blocks of 5 waves, two per CU
+    "p3:3264": [1, 1, 204, 51, 8, 1, 0, 255, 1, 512],
+    "p3:3265": [1, 1, 0, 0, 8, 0, 0, 205, 2, 320],
+    # 2 inclined planets, 32 walkers per group: 2304 is 72 groups and 4096 is 128, 256 is not > 256: still cx.
+    # 4097: 129 groups, crowded: lsx with nb = ceil(258 / 8) = 33, 129 + 33 = 162 blocks
+    "i2:2304": [1, 1, 0, 0, 8, 0, 0, 72, 2, 320],
+    "i2:4096": [1, 1, 0, 0, 8, 0, 0, 128, 2, 320],
+    "i2:4097": [2, 0, 129, 33, 8, 0, 1, 162, 1, 512],
+})
 
 
 @pytest.mark.parametrize("shape", sorted(PINS))
