@@ -9,17 +9,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "rvel-mcmc_amd"), os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")]
 import torch  # noqa: E402
 
-import test_gpu_resolve as T  # noqa: E402
-from conftest import s2_obs_oracle  # noqa: E402
+import oracle as O  # noqa: E402
+import support as T  # noqa: E402
+from conftest import S2_PLANETS, s2_obs_oracle  # noqa: E402
 
 obs = s2_obs_oracle()
 W = 6144
 X = T.wide_walkers(W)
 for res in ((0.0, 0), (T.TOL, 0), (T.TOL, 1), (T.TOL, 4)):
-    plan, dt, mult = T._plan(obs, W, resolve=res)
-    got, st = T._run(plan, X)
+    plan, dt, mult = T.adaptive_plan(S2_PLANETS, obs, W, resolve=res)
+    got, st = T.launch(plan, X)
     f = plan.faults(reset=True)
-    ref, st_ref, rf, est, margin = T._adapt_oracle(T._oracle_P(X), obs, dt, mult, res[0], res[1])
+    ref, st_ref, rf, est, margin = T._par(lambda p: O.logl_whx_adapt_batch(p, 2, obs, dt, mult, res[0], res[1]),
+                                          T.oracle_params(X, 2))
     mism = np.nonzero(st != st_ref)[0]
     ok = (st == 0) & (st_ref == 0)
     with np.errstate(invalid="ignore"):

@@ -1,6 +1,6 @@
 """Steady-state ensembles of the HD155358 and 3-planet chains (the device sampler, 512 walkers,
-1000 iterations from the tight ball: the procedure of tests/test_gpu_ias15_decisions.py
-_burned_in), saved for the CPU studies of the adaptive resolution's certain-reject bound on those
+1000 iterations from the tight ball: the procedure of tests/support.py
+burned_in), saved for the CPU studies of the adaptive resolution's certain-reject bound on those
 systems (tests/test_ias15_parity_harness.py, scripts/probe/cut_ratio_study.py):
 scripts/probe/ens_hd155358_it1000.npy and ens_3planet_it1000.npy ([512][Nvars], State order)."""
 import os
@@ -14,7 +14,7 @@ OUT = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "scripts", "probe
 
 
 def main():
-    from test_gpu_ias15_decisions import THIRD, _burned_in, _hd
+    from support import THIRD, burned_in as _burned_in, hd_system as _hd
 
     import oracle as O
     from conftest import S2_PLANETS

@@ -26,6 +26,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 import oracle as O
+from support import free_params_to_oracle as to_oracle  # noqa: F401  (the tests and scripts call it by this name)
+from support import report_line
 
 MARGIN = 1e-6  # walkers with |lnpdiff - ln U| < 1e-6 are exempt (counted)
 ROUNDOFF_REL = 1e-9  # IAS15 logL response to a 1e-15 relative input nudge, relative to max(1, |logL|)
@@ -80,19 +82,6 @@ def ias15_roundoff(P, n_planets, obs, ref, hill=1.0, has_inc=0):
         sens[both] = np.maximum(sens[both], np.abs(r2[both] - ref[both]) / np.maximum(1.0, np.abs(ref[both])))
         sens[s2 != st0] = np.inf
     return sens
-
-
-def to_oracle(pm, X):
-    """Free-parameter rows X [W][dim] of a State's ParamMap -> oracle layout [W][np][7]."""
-    if len(X) == 0:
-        return np.zeros((0, pm.n_planets, 7))
-    K = np.stack([pm.vector_to_kernel_np(x) for x in np.asarray(X, dtype=np.float64)], 1)  # [rows][W]
-    rows = 7 if pm.inclined else 5
-    W = K.shape[1]
-    out = np.zeros((W, pm.n_planets, 7))
-    for p in range(pm.n_planets):
-        out[:, p, :rows] = K[rows * p:rows * (p + 1)].T
-    return out
 
 
 def stretch_proposal(x, c, u1, u2, a=2.0):
@@ -197,10 +186,6 @@ class Tally:
              "max_abs_dlogl_ok_proposals_not_roundoff": getattr(self, "max_dlogl_ok_not_roundoff", 0.0),
              "unresolved_device": self.n_unresolved, "margin": MARGIN, "roundoff_rel": ROUNDOFF_REL}
         d.update(extra)
-        line = json.dumps(d)
-        print(line)
-        path = os.environ.get("RVM_PARITY_REPORT")
-        if path:
-            with open(path, "a") as f:
-                f.write(line + "\n")
+        print(json.dumps(d))
+        report_line("RVM_PARITY_REPORT", **d)
         return d

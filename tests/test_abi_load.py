@@ -6,32 +6,13 @@ import os
 import re
 
 from conftest import ROOT
+from support import header_prototypes, header_source
 
 from rvmcmc import _lib
 
 
-def header_source():
-    """include/rvmcmc.h without its comments."""
-    src = open(os.path.join(ROOT, "include", "rvmcmc.h")).read()
-    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-
-
 def header_functions():
     return sorted(set(re.findall(r"\b(rvm_[a-z_0-9]+)\s*\(", header_source())))
-
-
-def header_prototypes():
-    """{name: (return type, [(argument type, argument name), ...])} of every prototype the header declares;
-    a type is its C spelling without `const` and without blanks (`double*`, `rvm_plan**`, `int32_t`)."""
-    out = {}
-    for ret, name, args in re.findall(r"^(int|void|size_t|const char\*)\s+(rvm_\w+)\s*\(([^)]*)\)\s*;",
-                                      header_source(), flags=re.M):
-        out[name] = (ret, [])
-        for a in args.split(","):
-            m = re.match(r"(.*?)(\w+)$", " ".join(a.split()))
-            if m.group(0) != "void":
-                out[name][1].append((m.group(1).replace("const ", "").replace(" ", ""), m.group(2)))
-    return out
 
 
 def header_defines():

@@ -20,7 +20,7 @@ import sys
 import pytest
 import torch  # noqa: F401  (before librvmcmc.so is loaded: the process then holds one HIP runtime, torch's)
 from conftest import GOLDEN, S2_PLANETS, s2_obs_oracle
-from test_abi_load import header_prototypes
+from support import adaptive_plan, header_prototypes
 
 from rvmcmc import _lib
 
@@ -373,12 +373,7 @@ def make_plan():
     """The adaptive S2 plan of the second half (engine.LoglPlan; close() it)."""
     from rvmcmc import engine
 
-    obs = s2_obs_oracle()
-    cfg = engine.IntegratorConfig()
-    dt, mult, hint = cfg.plan_args(S2_PLANETS)
-    t, rv, er = engine.obs_arrays(obs)
-    plan = engine.LoglPlan(t, rv, er, obs.Npoints, 2, dt, mult, MAX_WALKERS, period_hint=hint,
-                           resolve=cfg.resolve(S2_PLANETS))
+    plan, _, _ = adaptive_plan(S2_PLANETS, s2_obs_oracle(), MAX_WALKERS, engine.IntegratorConfig().resolve(S2_PLANETS))
     assert plan.resolve_tol > 0.0 and plan.rows == 10
     return plan
 

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import chain_ref as R
+from support import refusal_text as _err
 from rvmcmc import _lib, chain, driver
 
 CASES = list(range(len(R.AR1_CASES)))
@@ -95,11 +96,6 @@ def test_split_rhat_of_identical_halves_is_below_one():
 
 
 # ---- (c) argument errors: < 0 before any HIP call, the argument named ----------------------------------
-
-def _err(rc):
-    assert rc < 0
-    return _lib.load().rvm_last_error()
-
 
 def test_record_argument_errors():
     lib = _lib.load()

@@ -9,7 +9,6 @@ single-process run: the RNG is keyed by global walker index and the complement i
 global order.
 """
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -17,7 +16,8 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from conftest import S2_PLANETS, S2_SCALES
+from conftest import S2_PLANETS
+from support import THIRD, free_port as _free_port, tight_ball
 from philox_ref import stretch_uniforms
 
 W = 48
@@ -151,16 +151,9 @@ class SpecNumpyOps(FusedNumpyOps):
             s.pos_aos[h].copy_(s.pos[h].t())
 
 
-THIRD = {"m": 1e-3, "a": 2.6, "h": 0.05, "k": 0.0, "l": 1.0}  # scripts/configs_bench.py config 5
 DEFAULT = dict(W=W, planets=S2_PLANETS, iters=ITERS)
 # BASELINE config 5: 65536 walkers, 3 planets, sharded 8 ways (8192 walkers = 4096 per half per rank)
 CONFIG5 = dict(W=65536, planets=S2_PLANETS + [THIRD], iters=2)
-
-
-def _initial_positions(state, W):
-    rng = np.random.default_rng(3)
-    scales = np.array([S2_SCALES[k] for k in state.get_rawkeys()])
-    return state.get_params()[None] + 1e-3 * scales * rng.standard_normal((W, state.Nvars))
 
 
 def _run_sampler(fused=False, ckpt=None, cfg=DEFAULT):
@@ -172,7 +165,7 @@ def _run_sampler(fused=False, ckpt=None, cfg=DEFAULT):
     ops = {False: NumpyOps, True: FusedNumpyOps, "spec": SpecNumpyOps}
     ens = EnsembleSampler(W_, state, obs=None, seed=SEED, device="cpu", ops=ops[fused])
     assert ens.fused == bool(fused) and ens.speculating() == (fused == "spec")
-    ens.set_positions(_initial_positions(state, W_))
+    ens.set_positions(tight_ball(state, (W_,), 3))
     ens.compute_lnprob()
     if ckpt is None:
         for _ in range(iters):
@@ -200,14 +193,6 @@ def _worker(rank, world, port, out_dir, fused=False, ckpt=False, cfg=DEFAULT):
         np.savez(os.path.join(out_dir, f"rank{rank}.npz"), pos=pos, lnp=lnp, acc=acc.numpy())
     finally:
         dist.destroy_process_group()
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 @pytest.mark.parametrize("world,fused", [(2, False), (4, False), (2, True), (4, True), (1, "spec"), (2, "spec"),

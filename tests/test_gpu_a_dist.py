@@ -9,22 +9,17 @@ the GPU: the module sorts first among the GPU tests.  RCCL itself (the driver's 
 exercised here: two ranks cannot share one device under RCCL.
 """
 import os
-import socket
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+from support import free_port as _free_port
+
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _run(world, W, iters, out, timeout=240):

@@ -13,34 +13,20 @@ diagnostics(): tests/test_chain_ref_cpu.py shows that no window decision of the 
 (margins >= 0.19 against the ~1e-10 a device error of the bound above moves m - c tau(m)), so `window`
 is compared exactly; tau and ess at rtol 1e-9, rhat at rtol 1e-10.
 """
-import dataclasses
-
 import numpy as np
 import pytest
 
 import chain_ref as R
-from conftest import S2_PLANETS, S2_SCALES, s2_obs_oracle
+from conftest import S2_SCALES
+from support import rvm_lib, s2_state_and_obs, tight_ball as _start, to_device, torch_or_fail as _torch
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -53
 
 
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available()
-    return torch
-
-
-def _lib():
-    from rvmcmc import _lib
-
-    return _lib
-
-
 def _dev(a, dtype=np.float64):
-    return _torch().as_tensor(np.array(a, dtype=dtype, order="C"), device="cuda")  # (a copy: inputs stay read-only)
+    return to_device(a, dtype, copy=True)  # (a copy: inputs stay read-only)
 
 
 # ---- record -------------------------------------------------------------------------------------------
@@ -51,8 +37,8 @@ def _dev(a, dtype=np.float64):
 def test_record_is_numpy_indexing(col_stride, src_col0, n_cols, with_lnp):
     """Two segments (two sources) into one slot of a three-slot chain: the slot equals numpy's strided
     indexing bit for bit, everything else keeps its NaN fill."""
-    torch, L = _torch(), _lib()
-    lib = L.load()
+    torch = _torch()
+    L, lib = rvm_lib()
     P, ld = 3, src_col0 + (n_cols - 1) * col_stride + 4
     rng = np.random.default_rng(1000 * col_stride + 10 * src_col0 + n_cols)
     srcs = [rng.standard_normal((P, ld)) for _ in range(2)]
@@ -115,8 +101,8 @@ def _shape_case(shape):
 
 
 def _device_moments(xd, P, W, t0, t1):
-    torch, L = _torch(), _lib()
-    lib = L.load()
+    torch = _torch()
+    L, lib = rvm_lib()
     outs = []
     for _ in range(2):
         mean = torch.full((P * W + 4,), -7.0, dtype=torch.float64, device="cuda")
@@ -132,8 +118,8 @@ def _device_moments(xd, P, W, t0, t1):
 
 
 def _device_autocov(xd, mean, P, W, t0, t1, lag0, n_lags):
-    torch, L = _torch(), _lib()
-    lib = L.load()
+    torch = _torch()
+    L, lib = rvm_lib()
     nws = lib.rvm_chain_autocov_workspace_bytes(P, W, n_lags) // 8
     assert nws >= P * n_lags
     outs = []
@@ -280,16 +266,7 @@ def test_recorder_thin_stride_capacity():
 # ---- end to end: fixed-step plan --------------------------------------------------------------------------
 
 def _state_and_obs(**kw):
-    from rvmcmc import engine, state
-
-    s = state.State(planets=[dict(p) for p in S2_PLANETS], **kw)
-    s.integrator = dataclasses.replace(engine.DEFAULT_CONFIG, resolve_tol=0.0)  # the fixed-step plan
-    return s, s2_obs_oracle()
-
-
-def _start(s, shape, seed):
-    sc = np.array([S2_SCALES[k] for k in s.get_rawkeys()])
-    return s.get_params() + 1e-3 * sc * np.random.default_rng(seed).standard_normal(shape + (s.Nvars,))
+    return s2_state_and_obs(fixed_step=True, **kw)
 
 
 def _run_pair(make, snapshot, n_steps=12, thin=3):

@@ -16,12 +16,11 @@ import pytest
 
 import ias15_parity as IP
 import oracle as O
-from conftest import S2_PLANETS, S2_SCALES
-from test_gpu_resolve import assert_t1_adaptive
+from conftest import S2_PLANETS
+from support import THIRD, assert_t1_adaptive, tight_ball
 
 pytestmark = pytest.mark.gpu
 
-THIRD = {"m": 1e-3, "a": 2.6, "h": 0.05, "k": 0.0, "l": 1.0}  # scripts/configs_bench.py config 5
 T2_ABS = 1e-6
 
 
@@ -37,9 +36,7 @@ def test_config5_shard_8192_walkers():
     s = State(planets=[dict(p) for p in planets])
     pm = s.param_map()
     W = 8192
-    rng = np.random.default_rng(7)
-    scales = np.array([S2_SCALES[k] for k in s.get_rawkeys()])
-    X0 = s.get_params()[None] + 1e-3 * scales * rng.standard_normal((W, s.Nvars))
+    X0 = tight_ball(s, (W,), 7)
     ens = EnsembleSampler(W, s, obs, seed=2024)
     ens.set_positions(X0)
     for _ in range(4):

@@ -13,30 +13,23 @@ the plan's side stream (rvm_refine.hip eager_kernel; VERDICT r4 weak 5, ADVICE r
 The reference's counterpart is the synchronous emcee callback (mcmc.py:28-35): it returns a finished
 logp before the caller touches the walker again.
 """
-import os
-
 import numpy as np
 import pytest
 
 import oracle as O
 from conftest import S2_PLANETS, s2_obs_oracle
-from test_gpu_resolve import RMAX, TOL, _oracle_P, _plan, wide_walkers
+from support import NONFINITE_WALKERS, RMAX, TOL, adaptive_plan, oracle_params, s2_state, steady_ensemble, switches
+from support import to_device, torch_or_fail as _torch, wide_walkers
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 
-
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available()
-    return torch
+def _plan(obs, W, resolve=(TOL, RMAX)):
+    return adaptive_plan(S2_PLANETS, obs, W, resolve)
 
 
 def _rows(X):
-    torch = _torch()
-    return torch.as_tensor(np.ascontiguousarray(X.T), device="cuda")
+    return to_device(X.T)
 
 
 @pytest.mark.parametrize("W", [256, 6144])
@@ -88,15 +81,8 @@ def test_eager_launch_is_complete_when_the_stream_is():
     torch = _torch()
     obs = s2_obs_oracle()
     W = 256
-    old = os.environ.get("RVM_EAGER")
-    os.environ["RVM_EAGER"] = "0"
-    try:
+    with switches({"RVM_EAGER": "0"}):
         ref_plan, _, _ = _plan(obs, W)
-    finally:
-        if old is None:
-            os.environ.pop("RVM_EAGER", None)
-        else:
-            os.environ["RVM_EAGER"] = old
     plan, _, _ = _plan(obs, W)
     cs = torch.cuda.Stream()
     K = torch.empty((10, W), dtype=torch.float64, device="cuda")
@@ -118,34 +104,21 @@ def test_eager_launch_is_complete_when_the_stream_is():
     assert f["refined"] > 0
 
 
-# two prior-passing walkers of the S2 observation set (hill_factor 0: no encounter exit) whose
-# halving passes blow up: [1] in pass 1 of its forward direction, [0] in pass 2 of both directions
-# (found on the oracle by scripts/probe/find_nonfinite_pass.py; rows m, a, h, k, l per planet)
-NONFINITE_WALKERS = np.array([
-    [[0.02256103, 0.41693664, -0.97022551, -0.02642071, 0.3], [0.00259106, 0.65391134, -0.90235793, 0.40896047, 2.2]],
-    [[0.00505582, 1.19118678, -0.39903947, 0.34994554, 0.3], [0.00316488, 1.01076266, -0.72163793, 0.31746809, 2.2]],
-])
-
-
 @pytest.mark.parametrize("W", [2, 64])
 def test_nonfinite_halving_pass_ends_the_walker(W):
     """A walker whose halving pass is non-finite ends NONFINITE after that pass, on the device as in
     the oracle (statuses equal; the plan counts it), beside ordinary wide-ball walkers whose results
     stay T1.  Before round 5 the kernel refined such a walker on to resolve_max = 12 (the last pass
     at 4096 x the base steps) where the oracle had stopped."""
-    from rvmcmc import engine
-
     torch = _torch()
     obs = s2_obs_oracle()
-    dt, mult, hint = engine.IntegratorConfig().plan_args(S2_PLANETS)
-    t, rv, er = engine.obs_arrays(obs)
     rmax = 12
-    plan = engine.LoglPlan(t, rv, er, obs.Npoints, 2, dt, mult, max(W, 2), period_hint=hint, resolve=(TOL, rmax))
+    plan, dt, mult = _plan(obs, max(W, 2), resolve=(TOL, rmax))
     X = np.concatenate([NONFINITE_WALKERS.reshape(2, 10), wide_walkers(64, ball=0.02, seed=9)[:W - 2]])
     lp, st, _ = plan.logl(_rows(X), hill_factor=0.0)
     torch.cuda.synchronize()
     got, gst = lp.cpu().numpy(), st.cpu().numpy()
-    ref, st_ref, rf, _, _ = O.logl_whx_adapt_batch(_oracle_P(X), 2, obs, dt, mult, TOL, rmax, 0.0)
+    ref, st_ref, rf, _, _ = O.logl_whx_adapt_batch(oracle_params(X, 2), 2, obs, dt, mult, TOL, rmax, 0.0)
     assert st_ref[0] == 3 and st_ref[1] == 3, (st_ref[:2], rf[:2])
     np.testing.assert_array_equal(gst[:2], [3, 3])
     assert np.all(np.isneginf(got[:2]))
@@ -213,15 +186,12 @@ def test_skipped_variants_are_exactly_the_ruled_out_ones():
     from rvmcmc import _lib
     from rvmcmc.ensemble import EnsembleSampler
     from rvmcmc.observations import FakeObservation
-    from rvmcmc.state import State
 
-    X0 = np.load(os.path.join(HERE, "..", "scripts", "probe", "ens_it2000.npy"))
+    X0 = steady_ensemble("s2")
 
     def run(skip):
-        old = os.environ.get("RVM_SKIP_VARIANTS")
-        os.environ["RVM_SKIP_VARIANTS"] = "1" if skip else "0"
-        try:
-            s = State(planets=[dict(p) for p in S2_PLANETS])
+        with switches({"RVM_SKIP_VARIANTS": "1" if skip else "0"}):
+            s = s2_state()
             np.random.seed(2017)
             obs = FakeObservation(s, Npoints=100, error=1.5e-4, errorVar=2.5e-5, tmax=120.)  # (its own plan)
             ens = EnsembleSampler(len(X0), s, obs, seed=2017)
@@ -236,11 +206,6 @@ def test_skipped_variants_are_exactly_the_ruled_out_ones():
                 out.append((it, ens._st_spec.cpu().numpy().copy(), ens._lnp_spec.cpu().numpy().copy(),
                             ens._dec.cpu().numpy().copy()))
             return ens, out
-        finally:
-            if old is None:
-                os.environ.pop("RVM_SKIP_VARIANTS", None)
-            else:
-                os.environ["RVM_SKIP_VARIANTS"] = old
 
     ea, oa = run(True)
     eb, ob = run(False)

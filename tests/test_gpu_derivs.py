@@ -31,10 +31,12 @@ import pytest
 
 import oracle as O
 from conftest import GOLDEN, S2_PLANETS, s2_obs_oracle
-from test_gpu_logl import LEVELS, SPO, T1_REL, _ball, _kernel_params, _plan, _torch
+from support import LEVELS, SPO, fixed_plan as _plan, kernel_rows as _kernel_params, oracle_params
+from support import pal_ball as _ball, t1_tol, torch_or_fail as _torch
 
 pytestmark = pytest.mark.gpu
 
+T1_REL = t1_tol(LEVELS)
 FLOOR = {0: 1e-4, 1: 1e-2, 2: 1e-2, 3: 1e-2, 4: 1.0, 5: 1e-2, 6: 1e-2}  # m a h k l ix iy (smala.FD_FLOOR)
 D1_GRAD, D1_HESS, D1_HESS_2ND = 1e-6, 1e-6, 1e-3
 SIG_STEP = 0.05
@@ -53,15 +55,6 @@ D2_GRAD, D2_HESS = 1e-4, 1e-4
 
 def _rows(np_, inclined):
     return 7 if inclined else 5
-
-
-def _flat_to_oracle(v, np_, rows):
-    """kernel-row vectors [N][rows*np] -> oracle params [N][np][7]"""
-    N = v.shape[0]
-    out = np.zeros((N, np_, 7))
-    for p in range(np_):
-        out[:, p, :rows] = v[:, rows * p:rows * (p + 1)]
-    return out
 
 
 def _fd_once(f, x, d, R):
@@ -107,7 +100,7 @@ def fd_derivs(logl_fn, x, np_, rows, rel=1e-3, d=None):
     if d is None:
         d = np.array([rel * max(abs(x[r]), FLOOR[r % rows]) for r in range(R)])
     pts = _stencil(x, d) + _stencil(x, 2 * d)
-    f = logl_fn(_flat_to_oracle(np.array(pts), np_, rows))
+    f = logl_fn(oracle_params(np.array(pts), np_, rows == 7))
     n = len(pts) // 2
     f0, g1, H1 = _fd_once(f[:n], x, d, R)
     _, g2, H2 = _fd_once(f[n:], x, 2 * d, R)

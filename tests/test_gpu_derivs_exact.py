@@ -30,16 +30,13 @@ per-epoch model RV, from which chi2, gradient and Hessian follow for any observa
 $RVM_DERIVS_EXACT_REPORT (a path) appends per case the kernel's largest scaled errors, the double
 restatement's and their ratio as JSON lines (profiles/derivs_exact_tier.jsonl).
 """
-import json
-import os
-
 import numpy as np
 import pytest
 from mpmath import mp
 
 import oracle as O
 import wh_ref as R
-from test_gpu_logl import T1_SENS_FACTOR, _torch, t1_tol
+from support import T1_SENS_FACTOR, report_line, t1_tol, torch_or_fail as _torch
 
 pytestmark = pytest.mark.gpu
 
@@ -91,13 +88,9 @@ def test_derivs_match_the_high_precision_truth(name, vec):
     ratio = max(eg, eH) / max(p["floor_grad"], p["floor_hess"])
     print(f"{name}/{vec}: kernel scaled errors grad {eg:.2e} hess {eH:.2e}; double restatement grad {p['floor_grad']:.2e} "
           f"hess {p['floor_hess']:.2e}; ratio {ratio:.2f} (bound {T1_SENS_FACTOR}); logp rel err {elp:.1e}; rv err {erv:.1e}")
-    path = os.environ.get("RVM_DERIVS_EXACT_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(json.dumps(dict(case=name, vector=vec, chains=C, kernel_grad=eg, kernel_hess=eH,
-                                    restatement_grad=p["floor_grad"], restatement_hess=p["floor_hess"], ratio=ratio,
-                                    bound=p["bound"], logp_rel_err=elp, logp_tol=t1_tol(tuple(c["levels"])),
-                                    rv_abs_err=erv, rv_tol=rv_tol)) + "\n")
+    report_line("RVM_DERIVS_EXACT_REPORT", case=name, vector=vec, chains=C, kernel_grad=eg, kernel_hess=eH,
+                restatement_grad=p["floor_grad"], restatement_hess=p["floor_hess"], ratio=ratio, bound=p["bound"],
+                logp_rel_err=elp, logp_tol=t1_tol(tuple(c["levels"])), rv_abs_err=erv, rv_tol=rv_tol)
     assert p["bound"] <= 1e-9
     assert elp <= t1_tol(tuple(c["levels"])), elp
     assert erv <= rv_tol, erv

@@ -22,85 +22,15 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import ROOT, S2_PLANETS, s2_obs_oracle
+from conftest import ROOT
+from support import HEDGE_RUNS, LAYOUTS, OFF, assert_same_run as _assert_same, hedge_run, hedge_sampler as _sampler
+from support import torch_or_fail as _torch, wide_walkers
 
 gpu = pytest.mark.gpu
 
-LAYOUTS = {"teams": {}, "split": {"RVM_REFINE_TEAMS": "0"}, "one_block": {"RVM_REFINE_SPLIT": "0"}}
-OFF = {"RVM_HEDGE": "0"}
-
-
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available()
-    return torch
-
-
-class _env:
-    """Environment switches read at plan creation, restored on exit."""
-
-    def __init__(self, env):
-        self.env = env
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.env}
-        os.environ.update(self.env)
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _sampler(X0, env):
-    from rvmcmc.ensemble import EnsembleSampler
-    from rvmcmc.state import State
-
-    with _env(env):
-        s = State(planets=[dict(p) for p in S2_PLANETS])
-        ens = EnsembleSampler(len(X0), s, s2_obs_oracle(), seed=2017)  # (a fresh observation set: a fresh plan)
-        ens.set_positions(X0)
-        ens.compute_lnprob()
-    ens.plan.faults(reset=True)
-    ens.plan.hedge_stats(reset=True)
-    return ens
-
-
-def _result(ens):
-    _torch().cuda.synchronize()
-    return (ens.gather_positions(), np.concatenate([l.cpu().numpy() for l in ens.lnp]), ens.naccepted.cpu().numpy(),
-            ens.plan.faults(reset=True), ens.plan.hedge_stats(reset=True))
-
-
-_RUNS = {}
-
 
 def _run(kind, env, iters):
-    """The sampler's result after `iters` iterations from the steady-state ensemble or a wide ball of n
-    walkers per half (kind = n), under the switches env; computed once per (kind, env)."""
-    key = (kind, tuple(sorted(env.items())), iters)
-    if key not in _RUNS:
-        if kind == "steady":
-            X0 = np.load(os.path.join(ROOT, "scripts", "probe", "ens_it2000.npy"))
-        else:
-            from test_gpu_resolve import wide_walkers
-
-            X0 = wide_walkers(2 * kind, ball=0.3, seed=5)
-        ens = _sampler(X0, env)
-        for _ in range(iters):
-            ens.step()
-        _RUNS[key] = _result(ens)
-    return _RUNS[key]
-
-
-def _assert_same(got, want):
-    np.testing.assert_array_equal(got[0], want[0])
-    np.testing.assert_array_equal(got[1], want[1])
-    np.testing.assert_array_equal(got[2], want[2])
-    assert got[3] == want[3], (got[3], want[3])
+    return hedge_run(HEDGE_RUNS, kind, env, iters)
 
 
 @gpu
@@ -143,8 +73,6 @@ def test_hedged_launch_is_complete_when_the_stream_is():
     """A hedged half-step on a stream of the caller's: right after that stream is synchronised the
     caller overwrites the complement half, which the hedge blocks read, with NaN; the half-step's
     results, and those of the next one on restored walkers, equal a plan's without the hedge."""
-    from test_gpu_resolve import wide_walkers
-
     torch = _torch()
     X0 = wide_walkers(128, ball=0.3, seed=7)
     cs = torch.cuda.Stream()
@@ -172,8 +100,6 @@ def test_hedged_launch_is_complete_when_the_stream_is():
 def test_hedged_launch_captures_into_a_graph():
     """A hedged half-step (fork, hedge kernel, likelihood kernel, refinement kernel, join, generation
     bump) captured into a graph: three replays give the bits of three plain launches without the hedge."""
-    from test_gpu_resolve import wide_walkers
-
     torch = _torch()
     X0 = wide_walkers(128, ball=0.3, seed=9)
     ens, ref = _sampler(X0, {}), _sampler(X0, OFF)

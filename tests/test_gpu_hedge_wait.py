@@ -24,12 +24,11 @@ import sys
 import numpy as np
 import pytest
 
-import test_gpu_hedge as H
 from conftest import ROOT
+from support import HEDGE_RUNS, LAYOUTS, OFF, assert_same_run, hedge_run, hedge_sampler, torch_or_fail, wide_walkers
 
 gpu = pytest.mark.gpu
 
-LAYOUTS, OFF = H.LAYOUTS, H.OFF
 MODES = {"unset": None, "0": "0", "2": "2"}
 ZERO = dict(waited=0, late_hits=0, gave_way=0)
 
@@ -44,32 +43,13 @@ PARENT = {
 }
 
 
-class _env:
-    """Environment switches read at plan creation (None: unset), restored on exit."""
-
-    def __init__(self, env):
-        self.env = env
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.env}
-        for k, v in self.env.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+def _waits(ens):
+    return ens.plan.hedge_waits(reset=True)
 
 
 def _sampler(X0, env):
-    with _env(env):
-        ens = H._sampler(X0, {})
-    ens.plan.hedge_waits(reset=True)
+    ens = hedge_sampler(X0, env)
+    _waits(ens)
     return ens
 
 
@@ -78,24 +58,17 @@ _RUNS = {}
 
 def _run(kind, layout, mode, iters):
     """As test_gpu_hedge._run, with the wait's mode set or unset at plan creation and its counters appended."""
-    key = (kind, layout, mode, iters)
-    if key not in _RUNS:
-        if kind == "steady":
-            X0 = np.load(os.path.join(ROOT, "scripts", "probe", "ens_it2000.npy"))
-        else:
-            from test_gpu_resolve import wide_walkers
+    return hedge_run(_RUNS, kind, {**LAYOUTS[layout], "RVM_HEDGE_WAIT": MODES[mode]}, iters, _waits)
 
-            X0 = wide_walkers(2 * kind, ball=0.3, seed=5)
-        ens = _sampler(X0, {**LAYOUTS[layout], "RVM_HEDGE_WAIT": MODES[mode]})
-        for _ in range(iters):
-            ens.step()
-        _RUNS[key] = H._result(ens) + (ens.plan.hedge_waits(reset=True),)
-    return _RUNS[key]
+
+def _off(kind, layout, iters):
+    """The run without the hedge, from (or into) test_gpu_hedge.py's cache."""
+    return hedge_run(HEDGE_RUNS, kind, {**LAYOUTS[layout], **OFF}, iters)
 
 
 def _check(tag, on, off):
     print(f"[hedge wait {tag}] counters {on[3]} hedge {on[4]} waits {on[5]}")
-    H._assert_same(on, off)
+    assert_same_run(on, off)
     assert on[3]["handoff_timeouts"] == 0 and on[3]["nonfinite"] == off[3]["nonfinite"], on[3]
     w = on[5]
     assert w["waited"] == w["late_hits"] + w["gave_way"], w
@@ -105,7 +78,7 @@ def _check(tag, on, off):
 @gpu
 @pytest.mark.parametrize("mode", list(MODES))
 def test_steady_state_bit_identical_with_teams(mode):
-    off = H._run("steady", {**LAYOUTS["teams"], **OFF}, 4)
+    off = _off("steady", "teams", 4)
     on = _run("steady", "teams", mode, 4)
     w = _check(f"steady teams mode {mode}", on, off)
     assert off[3]["refined"] > 0 and off[3]["handoff_timeouts"] == 0
@@ -122,7 +95,7 @@ def test_steady_state_bit_identical_with_teams(mode):
 @pytest.mark.parametrize("mode", list(MODES))
 @pytest.mark.parametrize("layout", ["split", "one_block"])
 def test_steady_state_layouts_without_teams_never_wait(layout, mode):
-    off = H._run("steady", {**LAYOUTS[layout], **OFF}, 4)
+    off = _off("steady", layout, 4)
     on = _run("steady", layout, mode, 4)
     w = _check(f"steady {layout} mode {mode}", on, off)
     assert w == ZERO, w
@@ -135,7 +108,7 @@ def test_steady_state_layouts_without_teams_never_wait(layout, mode):
 def test_smallest_shapes(n, mode):
     """Every slot hedged, the last hedge group partial; groups mix ready, late and deeper (pass 3) walkers, so
     trials fail after a wait."""
-    off = H._run(n, {**LAYOUTS["teams"], **OFF}, 3)
+    off = _off(n, "teams", 3)
     on = _run(n, "teams", mode, 3)
     _check(f"{n} per half mode {mode}", on, off)
     assert off[3]["refined"] > 0
@@ -146,11 +119,9 @@ def test_smallest_shapes(n, mode):
 def test_hedged_launch_with_the_wait_captures_into_a_graph():
     """test_gpu_hedge.test_hedged_launch_captures_into_a_graph with every trial going through the poll loop:
     three replays of the captured launch give the bits of three plain launches without the hedge."""
-    from test_gpu_resolve import wide_walkers
-
-    torch = H._torch()
+    torch = torch_or_fail()
     X0 = wide_walkers(128, ball=0.3, seed=9)
-    ens, ref = _sampler(X0, {"RVM_HEDGE_WAIT": "2"}), H._sampler(X0, OFF)
+    ens, ref = _sampler(X0, {"RVM_HEDGE_WAIT": "2"}), hedge_sampler(X0, OFF)
     ens.half_step(ens.pos[0], ens.lnp[0], ens.pos[1], 0)  # (a plain launch first: lazily created state is in place)
     ref.half_step(ref.pos[0], ref.lnp[0], ref.pos[1], 0)
     torch.cuda.synchronize()

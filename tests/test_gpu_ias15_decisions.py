@@ -22,8 +22,10 @@ import pytest
 
 import ias15_parity as IP
 import oracle as O
-from conftest import S2_PLANETS, S2_SCALES, s2_obs_oracle
+from conftest import S2_PLANETS, s2_obs_oracle
 from philox_ref import stretch_uniforms
+from support import THIRD, burned_in as _burned_in, hd_system as _hd, steady_ensemble, tight_ball
+from support import torch_or_fail as _torch
 
 pytestmark = pytest.mark.gpu
 
@@ -31,26 +33,6 @@ pytestmark = pytest.mark.gpu
 # reach further from the plan's initial state than the tight balls of tests/test_gpu_logl.py
 # (5e-8 there); measured max ~1e-7 on the bench config after a few iterations (reported per test)
 T2_ABS = 1e-6
-THIRD = {"m": 1e-3, "a": 2.6, "h": 0.05, "k": 0.0, "l": 1.0}  # scripts/configs_bench.py config 5
-HD_SOL = [6.57730330e-01, -9.72263877e-02, -7.82798396e-02, 8.84031737e-04, 4.42804990e+00,
-          1.04404207e+00, -2.05622789e-02, -1.08797961e-01, 8.30379710e-04, 1.49919861e+00]
-
-
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available()
-    return torch
-
-
-def _hd():
-    import os
-
-    from conftest import GOLDEN
-
-    planets = [{"m": HD_SOL[3], "a": HD_SOL[0], "h": HD_SOL[1], "k": HD_SOL[2], "l": HD_SOL[4]},
-               {"m": HD_SOL[8], "a": HD_SOL[5], "h": HD_SOL[6], "k": HD_SOL[7], "l": HD_SOL[9]}]
-    return planets, O.obs_from_file(os.path.join(GOLDEN, "HD155358.vels"), Npoints=100)
 
 
 def _device_logl(ens_or_plan, pm, Q, hill):
@@ -85,10 +67,8 @@ def stretch_parity(name, planets, obs, W, ball, iterations=2, warm=4, roundoff=F
     s = State(planets=[dict(p) for p in planets])
     pm = s.param_map()
     dim = s.Nvars
-    scales = np.array([S2_SCALES[k] for k in s.get_rawkeys()])
     if X0 is None:
-        rng = np.random.default_rng(ball_seed)
-        X0 = s.get_params()[None] + ball * scales * rng.standard_normal((W, dim))
+        X0 = tight_ball(s, (W,), ball_seed, ball)
     ens = EnsembleSampler(W, s, obs, seed=seed)
     ens.set_positions(X0)
     ens.compute_lnprob()
@@ -200,11 +180,7 @@ def test_stretch_vs_ias15_steady_state():
     (eccentricities to 0.45) and the plan's fixed step alone missed T2 on 668 of 5823 proposals.  Two
     speculative iterations of the real sampler; every decision and every OK proposal's logL against
     IAS15 (the adaptive resolution's regime: extensions, halving passes, certain rejects)."""
-    import os
-
-    from conftest import ROOT
-
-    X0 = np.load(os.path.join(ROOT, "scripts", "probe", "ens_it2000.npy"))
+    X0 = steady_ensemble("s2")
     tally, info = stretch_parity("stretch/steady-state S2 4096 walkers (iteration 2000)", S2_PLANETS, s2_obs_oracle(),
                                  len(X0), 0.0, warm=0, roundoff=True, X0=X0)
     rep = tally.report(**info)
@@ -215,26 +191,6 @@ def test_stretch_vs_ias15_steady_state():
     assert rep["max_abs_dlogl_ok_proposals_not_roundoff"] <= T2_ABS
     assert rep["exempt_status_disagreement"] <= max(4, rep["decisions"] // 500)
     assert rep["differing_but_exempt"] == 0 and rep["exempt_current_status_disagreement"] == 0
-
-
-def _burned_in(planets, obs, W, iters, seed=2017):
-    """An ensemble after `iters` iterations of the device sampler from the tight ball (the chain's
-    steady state, the regime of the adaptive resolution)."""
-    torch = _torch()
-    from rvmcmc.ensemble import EnsembleSampler
-    from rvmcmc.state import State
-
-    s = State(planets=[dict(p) for p in planets])
-    scales = np.array([S2_SCALES[k] for k in s.get_rawkeys()])
-    X0 = s.get_params()[None] + 1e-3 * scales * np.random.default_rng(1).standard_normal((W, s.Nvars))
-    ens = EnsembleSampler(W, s, obs, seed=seed + 1)
-    ens.set_positions(X0)
-    ens.compute_lnprob()
-    for _ in range(iters):
-        ens.step()
-    torch.cuda.synchronize()
-    ens.check_faults()
-    return ens.gather_positions()
 
 
 @pytest.mark.parametrize("case", ["HD155358", "3-planet"])

@@ -18,64 +18,16 @@ import pytest
 
 import oracle as O
 from conftest import GOLDEN, S2_PLANETS, s2_obs_oracle
+from support import EXTRA_PLANETS, LEVELS, SPO, T1_SENS_FACTOR, fixed_plan as _plan, kernel_rows as _kernel_params
+from support import pal_ball as _ball, current_test, report_line, t1_tol, torch_or_fail as _torch
 
 pytestmark = pytest.mark.gpu
 
-# T1: roundoff floor.  ~1e-15 relative differences in the per-level model RV (FMA contraction on
-# the GPU, a different Stumpff evaluation) are amplified by the Richardson weights (sum_k |w_k|:
-# 6.2 at 4 levels, 26 at 6) and by the likelihood's conditioning (dlogL/drv ~ 2 sum|r|/(N sigma^2)
-# ~ 1e4).  Tolerance: 1e-11 * sum|w| * max(1, |logL|)  (measured max 4e-11 at 4 levels).
-T1_REL_PER_W = 1e-11
-# T1 as used by the batch comparisons below: 3x the oracle's own roundoff sensitivity over the
-# batch (t1_tol_sens).  SURVEY.md §8c's 1e-12 is below that sensitivity for these walkers (the
-# oracle itself moves by up to 7.5e-11 when an input changes by 1e-15 relative), so it cannot be
-# met by any second implementation; t1_tol (the Sigma|w| form above) remains for the sampler and
-# derivative tests that compare single values.
-T1_SENS_FACTOR = 3.0
 T2_ABS = 5e-8
-# default integrator (rvmcmc.engine.IntegratorConfig): level multipliers and base steps per orbit
-LEVELS = (4, 5, 6, 7)
-SPO = 8.0
 # model RV: per-level differences of ~1e-14 absolute (roundoff accumulated over thousands of
 # steps) times the weights' sum|w| (6.2 harmonic 4 levels, 35 for 4..7)
 T1_RV_ABS = 1e-14 * float(np.abs(O.richardson_weights(LEVELS)).sum())
-
-
-def t1_tol(nl=LEVELS):
-    return T1_REL_PER_W * float(np.abs(O.richardson_weights(nl)).sum())
-
-
 T1_REL = t1_tol(LEVELS)
-
-
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch
-
-
-def _plan(obs, planets, n_levels=LEVELS, steps=SPO, max_walkers=4096, inclined=False):
-    from rvmcmc import engine
-
-    pmin = engine.min_period(planets)
-    dt = pmin / steps
-    t, rv, er = engine.obs_arrays(obs)
-    return engine.LoglPlan(t, rv, er, obs.Npoints, len(planets), dt, n_levels, max_walkers,
-                           period_hint=pmin, inclined=inclined), dt
-
-
-def _ball(planets, W, rel=1e-3, seed=0):
-    rng = np.random.default_rng(seed)
-    base = O.pal_params(planets)
-    P = np.repeat(base[None], W, 0)
-    P[:, :, :5] *= 1 + rel * rng.standard_normal((W, len(planets), 5))
-    return P  # [W][np][7]
-
-
-def _kernel_params(P, rows=5):
-    W, n, _ = P.shape
-    return np.ascontiguousarray(np.concatenate([P[:, p, :rows].T for p in range(n)], 0))
 
 
 def _run(plan, P, hill=1.0, want_rv=False):
@@ -88,20 +40,16 @@ def _run(plan, P, hill=1.0, want_rv=False):
 
 def _t1_report(err, tol, nl, sens=None):
     """Append the measured T1 maximum of one comparison to $RVM_T1_REPORT (JSON lines)."""
-    path = os.environ.get("RVM_T1_REPORT")
-    if path:
-        import json
-
-        d = {"test": os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0],
-             "max_rel_err": float(err.max(initial=0.0)), "tol": float(tol),
-             "levels": list(np.atleast_1d(nl).tolist()), "sum_abs_w": float(np.abs(O.richardson_weights(nl)).sum())}
-        if sens is not None and len(err):
-            r = err / np.maximum(sens, 1e-300)
-            d.update(max_sens=float(sens.max()), min_sens=float(sens.min()), max_err_over_sens=float(r.max()),
-                     p99_err_over_sens=float(np.percentile(r, 99)), max_err_where_sens_zero=float(err[sens == 0].max(initial=0)),
-                     max_err_over_max_sens_1e12=float((err / np.maximum(sens, 1e-12)).max()))
-        with open(path, "a") as f:
-            f.write(json.dumps(d) + "\n")
+    if not os.environ.get("RVM_T1_REPORT"):
+        return
+    d = {"max_rel_err": float(err.max(initial=0.0)), "tol": float(tol),
+         "levels": list(np.atleast_1d(nl).tolist()), "sum_abs_w": float(np.abs(O.richardson_weights(nl)).sum())}
+    if sens is not None and len(err):
+        r = err / np.maximum(sens, 1e-300)
+        d.update(max_sens=float(sens.max()), min_sens=float(sens.min()), max_err_over_sens=float(r.max()),
+                 p99_err_over_sens=float(np.percentile(r, 99)), max_err_where_sens_zero=float(err[sens == 0].max(initial=0)),
+                 max_err_over_max_sens_1e12=float((err / np.maximum(sens, 1e-12)).max()))
+    report_line("RVM_T1_REPORT", test=current_test(), **d)
 
 
 NUDGES = [(0, 4, 1), (-1, 4, -1), (0, 1, 1), (-1, 1, -1), (0, 2, 1), (-1, 0, 1)]
@@ -201,10 +149,6 @@ def test_t1_levels(nl, spo):
     got, st, _ = _run(plan, P)
     ref, st_ref = O.logl_whx_batch(P, 2, obs, dt, nl)
     _assert_t1(got, st, ref, st_ref, nl, sens=oracle_sensitivity(P, 2, obs, dt, nl))
-
-
-EXTRA_PLANETS = [{"m": 1e-3, "a": 2.6, "h": 0.05, "k": 0.0, "l": 1.0},
-                 {"m": 5e-4, "a": 4.1, "h": -0.03, "k": 0.02, "l": 4.0}]
 
 
 @pytest.mark.parametrize("n_planets", [1, 3, 4])

@@ -28,25 +28,24 @@ import os
 import subprocess
 import sys
 
-import numpy as np
 import pytest
 
-from conftest import S2_PLANETS, S2_SCALES, s2_obs_oracle
+from conftest import S2_SCALES
+from support import s2_state_and_obs, tight_ball
 
 pytestmark = pytest.mark.gpu
 
 
 def build_and_step():
     import torch
-    from rvmcmc import engine, state
+    from rvmcmc import engine
     from rvmcmc.ensemble import EnsembleSampler
     from rvmcmc.mcmc import MhChains
     from rvmcmc.smala import SmalaChains
     from rvmcmc.tempering import PTSampler
 
-    s, obs = state.State(planets=[dict(p) for p in S2_PLANETS]), s2_obs_oracle()
-    sc = np.array([S2_SCALES[k] for k in s.get_rawkeys()])
-    X0 = s.get_params()[None] + 1e-3 * sc * np.random.default_rng(0).standard_normal((64, s.Nvars))
+    s, obs = s2_state_and_obs()
+    X0 = tight_ball(s, (64,), 0)
     ens = EnsembleSampler(64, s, obs, seed=1)
     ens.set_positions(X0)
     mh = MhChains(s, obs, S2_SCALES, 1e-3, n_chains=64, seed=2)

@@ -26,13 +26,9 @@ layout blocks stop on them; with the switch off, or without a hedge, none.  A bl
 launch writes more marks than it has hedge blocks.
 The hedge statistics depend on timing and are excluded from the equality.
 """
-import os
-
-import numpy as np
 import pytest
 
-from conftest import ROOT
-from test_gpu_hedge import _assert_same, _result, _sampler
+from support import assert_same_run as _assert_same, hedge_run
 
 pytestmark = pytest.mark.gpu
 
@@ -46,20 +42,7 @@ _RUNS = {}
 
 def _run(kind, env, iters):
     """test_gpu_hedge._run with the marks' counters as a sixth entry; computed once per (kind, env)."""
-    key = (kind, tuple(sorted(env.items())), iters)
-    if key not in _RUNS:
-        if kind == "steady":
-            X0 = np.load(os.path.join(ROOT, "scripts", "probe", "ens_it2000.npy"))
-        else:
-            from test_gpu_resolve import wide_walkers
-
-            X0 = wide_walkers(2 * kind, ball=0.3, seed=5)
-        ens = _sampler(X0, env)
-        ens.plan.hedge_marks(reset=True)
-        for _ in range(iters):
-            ens.step()
-        _RUNS[key] = _result(ens) + (ens.plan.hedge_marks(reset=True),)
-    return _RUNS[key]
+    return hedge_run(_RUNS, kind, env, iters, lambda ens: ens.plan.hedge_marks(reset=True))
 
 
 @pytest.mark.parametrize("layout", list(LAYOUTS))

@@ -17,131 +17,29 @@ with every step halved, up to resolve_max times.  Checked here:
 Reference-physics (IAS15) accuracy of the rule over the proposals a sampler makes is in
 tests/test_gpu_ias15_decisions.py.
 """
-from concurrent.futures import ThreadPoolExecutor
+import os
 
 import numpy as np
 import pytest
 
 import oracle as O
-from conftest import S2_PLANETS, S2_SCALES, s2_obs_oracle
+from conftest import GOLDEN, S2_PLANETS, hd_planets, s2_obs_oracle
+from support import RMAX, TOL, _par, adaptive_plan, assert_t1_adaptive, launch as _run, oracle_params
+from support import s2_rows_and_scales as _x0, s2_state, steady_ensemble, switches, torch_or_fail as _torch, wide_walkers
 
 pytestmark = pytest.mark.gpu
 
-TOL, RMAX = 5e-7, 4
-T1_REL = 1e-11 * 35.0  # tests/test_gpu_logl.py: 1e-11 sum|w| (levels 4..7)
-
-
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available()
-    return torch
-
 
 def _plan(obs, W, resolve=(TOL, RMAX)):
-    from rvmcmc import engine
-
-    dt, mult, hint = engine.IntegratorConfig().plan_args(S2_PLANETS)
-    t, rv, er = engine.obs_arrays(obs)
-    return engine.LoglPlan(t, rv, er, obs.Npoints, 2, dt, mult, W, period_hint=hint, resolve=resolve), dt, mult
-
-
-def _x0():
-    return np.array([p[k] for p in S2_PLANETS for k in "mahkl"]), np.array([S2_SCALES[k] for _ in S2_PLANETS
-                                                                             for k in "mahkl"])
-
-
-def wide_walkers(W, ball=0.6, seed=3):
-    """Half a sampler-like ball (x0 + ball * scales * N(0,1), mcmc.py:45-51), half stretch
-    proposals between its members (q = c - z (c - x), z in [1/2, 2]): [W][10] kernel rows."""
-    x0, sc = _x0()
-    rng = np.random.default_rng(seed)
-    n = W // 2
-    X = x0 + ball * sc * rng.standard_normal((n, 10))
-    j = rng.integers(0, n, W - n)
-    z = (rng.random(W - n) + 1.0) ** 2 / 2.0
-    Q = X[j] - z[:, None] * (X[j] - X[:W - n])
-    return np.concatenate([X, Q])
+    return adaptive_plan(S2_PLANETS, obs, W, resolve)
 
 
 def _oracle_P(X):
-    P = np.zeros((len(X), 2, 7))
-    P[:, :, :5] = X.reshape(-1, 2, 5)
-    return P
-
-
-def _run(plan, X):
-    torch = _torch()
-    K = torch.as_tensor(np.ascontiguousarray(X.T), device="cuda")
-    lp, st, _ = plan.logl(K)
-    torch.cuda.synchronize()
-    return lp.cpu().numpy(), st.cpu().numpy()
-
-
-def _par(fn, P, nt=16):
-    idx = np.array_split(np.arange(len(P)), nt)
-    with ThreadPoolExecutor(nt) as ex:
-        parts = list(ex.map(lambda ix: fn(P[ix]), idx))
-    return [np.concatenate([p[k] for p in parts]) for k in range(len(parts[0]))]
-
-
-def _par_ix(fn, P, nt=16):
-    """_par for fn(P_chunk, index_chunk)."""
-    idx = np.array_split(np.arange(len(P)), nt)
-    with ThreadPoolExecutor(nt) as ex:
-        parts = list(ex.map(lambda ix: fn(P[ix], ix), idx))
-    return [np.concatenate([p[k] for p in parts]) for k in range(len(parts[0]))]
+    return oracle_params(X, 2)
 
 
 def _adapt_oracle(P, obs, dt, mult, tol=TOL, rmax=RMAX):
     return _par(lambda p: O.logl_whx_adapt_batch(p, 2, obs, dt, mult, tol, rmax), P)
-
-
-def assert_t1_adaptive(got, st, P, n_planets, obs, dt, mult, tol=TOL, rmax=RMAX, has_inc=0, ctx=None, ecc_guard=0.0):
-    """T1 of an adaptive-resolution launch against the oracle's restatement of the same rule
-    (oracle.logl_whx_adapt_batch): statuses and logL, up to sensitivity.  Chaotic walkers (close
-    approaches) and decisions at roundoff distance from their bound may legitimately go the other
-    way in a second implementation: the oracle's own response to 1e-15 relative input nudges (of
-    logL, of the status, of the stage reached and of the final estimate -- a difference of two
-    extrapolations, which near a close approach moves by up to tens of percent under such a nudge),
-    and its closest approach to any decision's bound.  ctx: the sampler's accept inputs (the
-    certain-reject cut; oracle.logl_whx_adapt_batch).  Returns (stages [W][2], sensitive [W]) and,
-    with ctx, the oracle's cut [W][2]."""
-    W = len(got)
-
-    def fn(p, ix=None):
-        c = None if ctx is None else dict(ctx, **{k: np.asarray(ctx[k])[ix] for k in ("mode", "z", "u", "lnp0")})
-        r = O.logl_whx_adapt_batch(p, n_planets, obs, dt, mult, tol, rmax, has_inc=has_inc, ctx=c, ecc_guard=ecc_guard)
-        return r if ctx is not None else r + (np.zeros((len(p), 2), dtype=np.int32),)
-
-    ref, st_ref, rf, est, margin, cut = _par_ix(fn, P)
-    sens = np.zeros(W)
-    flips = np.zeros(W, dtype=bool)
-    for pl, par, sgn in [(0, 4, 1), (-1, 4, -1), (0, 1, 1)]:
-        P2 = P.copy()
-        P2[:, pl, par] *= 1 + sgn * 1e-15
-        r2, s2, rf2, est2, _, cut2 = _par_ix(fn, P2)
-        flips |= (s2 != st_ref) | np.any(rf2 != rf, axis=1) | np.any(cut2 != cut, axis=1)
-        with np.errstate(invalid="ignore"):  # (an estimate whose roundoff response is not small
-            # against its distance from the bound)
-            flips |= np.any(np.abs(est2 - est) > 0.02 * np.abs(est - 0.5 * tol), axis=1)
-        both = (st_ref == 0) & (s2 == 0)
-        sens[both] = np.maximum(sens[both], np.abs(r2[both] - ref[both]) / np.maximum(1.0, np.abs(ref[both])))
-    sensitive = flips | (sens > 1e-9) | (margin.min(axis=1) < 1e-6)
-    mism = st != st_ref
-    assert np.all(~mism | sensitive), np.nonzero(mism & ~sensitive)
-    assert mism.sum() <= max(2, W // 100)
-    ok = (st == 0) & (st_ref == 0)
-    err = np.abs(got[ok] - ref[ok]) / np.maximum(1.0, np.abs(ref[ok]))
-    bound = np.maximum(T1_REL, 1e3 * sens[ok])
-    bad = (err > bound) & ~sensitive[ok]
-    assert not bad.any(), (np.nonzero(ok)[0][bad][:10], err[bad][:10])
-    assert np.mean(err <= T1_REL) > 0.9
-    # walkers the oracle leaves UNRESOLVED are UNRESOLVED on the device too (up to sensitivity)
-    assert np.all(((st == 4) == (st_ref == 4)) | sensitive)
-    if ctx is not None:
-        return rf, sensitive, cut
-    return rf, sensitive
 
 
 # a few walkers: the extension after the main pass (RVM_CX_MIN_WALKERS); 512: its concurrent wave in the
@@ -265,9 +163,8 @@ def test_certain_reject_cut_matches_oracle(W):
     import ias15_parity as IP
     from philox_ref import stretch_uniforms
     from rvmcmc.ensemble import EnsembleSampler
-    from rvmcmc.state import State
 
-    s = State(planets=[dict(p) for p in S2_PLANETS])
+    s = s2_state()
     obs = s2_obs_oracle()
     X0 = wide_walkers(W, ball=0.6, seed=13)
     ens = EnsembleSampler(W, s, obs, seed=5)
@@ -346,9 +243,7 @@ def test_t1_eccentricity_guard(W):
     obs = s2_obs_oracle()
     guard = engine.IntegratorConfig().ecc_guard(S2_PLANETS)
     assert 0.26 < guard < 0.27
-    dt, mult, hint = engine.IntegratorConfig().plan_args(S2_PLANETS)
-    t, rv, er = engine.obs_arrays(obs)
-    plan = engine.LoglPlan(t, rv, er, obs.Npoints, 2, dt, mult, W, period_hint=hint, resolve=(TOL, RMAX, guard))
+    plan, dt, mult = _plan(obs, W, resolve=(TOL, RMAX, guard))
     assert plan.ecc_guard == guard
     X = wide_walkers(W, ball=0.3, seed=21)
     got, st = _run(plan, X)
@@ -367,21 +262,18 @@ def test_refinement_layouts_bit_identical(system):
     iterations of the sampler at a steady state (extensions, halving passes, certain rejects,
     two-pass walkers; HD155358's launches climb to passes 3 and 4), positions, log-probabilities and
     plan counters compared."""
-    import os
-
-    from conftest import ROOT, hd_planets
     from rvmcmc.ensemble import EnsembleSampler
     from rvmcmc.state import State
 
     torch = _torch()
     if system == "s2":
         planets, obs = S2_PLANETS, s2_obs_oracle
-        X0 = np.load(os.path.join(ROOT, "scripts", "probe", "ens_it2000.npy"))
+        X0 = steady_ensemble("s2")
         iters = 4
     else:
         planets = hd_planets()
-        obs = lambda: O.obs_from_file(os.path.join(ROOT, "tests", "golden", "HD155358.vels"), Npoints=100)  # noqa: E731
-        X0 = np.load(os.path.join(ROOT, "scripts", "probe", "ens_hd155358_it1000.npy"))
+        obs = lambda: O.obs_from_file(os.path.join(GOLDEN, "HD155358.vels"), Npoints=100)  # noqa: E731
+        X0 = steady_ensemble("hd155358")
         iters = 6
     runs = []
     envs = [{}, {"RVM_REFINE_TEAMS": "2"}, {"RVM_REFINE_TEAMS": "4"}, {"RVM_REFINE_TEAMS": "0"},
@@ -389,9 +281,7 @@ def test_refinement_layouts_bit_identical(system):
     if system == "s2":
         envs.append({"RVM_REFINE_W4": "0"})  # (the eight-wave instantiation against the four-wave ones)
     for env in envs:
-        old = {k: os.environ.get(k) for k in env}
-        os.environ.update(env)
-        try:
+        with switches(env):
             s = State(planets=[dict(p) for p in planets])
             ens = EnsembleSampler(len(X0), s, obs(), seed=2017)  # (a fresh observation set: fresh plans)
             ens.set_positions(X0)
@@ -402,12 +292,6 @@ def test_refinement_layouts_bit_identical(system):
             torch.cuda.synchronize()
             runs.append((ens.gather_positions(), np.concatenate([l.cpu().numpy() for l in ens.lnp]),
                          ens.plan.faults(reset=True)))
-        finally:
-            for k, v in old.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
     assert runs[0][2]["refined"] > 0 and runs[0][2]["truncated"] > 0
     assert runs[0][2]["handoff_timeouts"] == 0
     for X, lp, f in runs[1:]:
@@ -421,15 +305,12 @@ def test_certain_reject_can_be_switched_off():
     short -- every open walker refines to the bound -- and the sampler still runs at the steady
     state."""
     import dataclasses
-    import os
 
-    from conftest import ROOT
     from rvmcmc.ensemble import EnsembleSampler
-    from rvmcmc.state import State
 
     torch = _torch()
-    X0 = np.load(os.path.join(ROOT, "scripts", "probe", "ens_it2000.npy"))
-    s = State(planets=[dict(p) for p in S2_PLANETS])
+    X0 = steady_ensemble("s2")
+    s = s2_state()
     s.integrator = dataclasses.replace(s.integrator, certain_reject=False)
     ens = EnsembleSampler(len(X0), s, s2_obs_oracle(), seed=2017)
     assert not ens.plan.certain_reject
@@ -449,25 +330,14 @@ def test_eager_halving_passes_bit_identical(W, passes):
     kernel replays them: the same logL, status bits and plan counters as the refinement kernel
     integrating them after the likelihood kernel (RVM_EAGER=0), on wide-ball walkers (extensions,
     one- and two-pass walkers, deeper ones, encounters, prior rejections)."""
-    import os
-
     obs = s2_obs_oracle()
     X = wide_walkers(W, ball=0.3, seed=5)
     res = []
     for env in ("1", "0"):
-        old = {k: os.environ.get(k) for k in ("RVM_EAGER", "RVM_EAGER_PASSES")}
-        os.environ["RVM_EAGER"] = env
-        os.environ["RVM_EAGER_PASSES"] = passes
-        try:
+        with switches({"RVM_EAGER": env, "RVM_EAGER_PASSES": passes}):
             plan, _, _ = _plan(obs, W)
             got, st = _run(plan, X)
             res.append((got, st, plan.faults(reset=True)))
-        finally:
-            for k, v in old.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
     np.testing.assert_array_equal(res[0][1], res[1][1])
     np.testing.assert_array_equal(res[0][0], res[1][0])
     assert res[0][2] == res[1][2], (res[0][2], res[1][2])

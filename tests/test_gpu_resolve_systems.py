@@ -15,7 +15,6 @@ state through the t = 0 hand-off and the lane save / load.  Here five systems --
 The layouts the sizes are meant to reach are pinned on the host by tests/test_logl_layout_host_cpu.py.
 """
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -23,21 +22,14 @@ import pytest
 import ias15_parity as IP
 import oracle as O
 from conftest import S2_PLANETS, S2_SCALES
-from test_gpu_logl import EXTRA_PLANETS
-from test_gpu_resolve import RMAX, T1_REL, TOL, assert_t1_adaptive
+from support import EXTRA_PLANETS, RMAX, T1_REL, TOL, adaptive_plan, assert_t1_adaptive, launch as _run, oracle_params
+from support import switches, torch_or_fail as _torch
 
 pytestmark = pytest.mark.gpu
 
 # name -> (planets, inclined)
 SYSTEMS = {"p3": (3, False), "p4": (4, False), "i2": (2, True), "i3": (3, True), "i4": (4, True)}
 BALL = 0.3
-
-
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available()
-    return torch
 
 
 def system_planets(name):
@@ -76,30 +68,11 @@ def system_walkers(name, W, ball=BALL, seed=3):
 
 
 def oracle_P(name, X):
-    n, inclined = SYSTEMS[name]
-    rows = 7 if inclined else 5
-    P = np.zeros((len(X), n, 7))
-    P[:, :, :rows] = np.asarray(X).reshape(-1, n, rows)
-    return P
+    return oracle_params(X, *SYSTEMS[name])
 
 
 def _plan(name, W):
-    from rvmcmc import engine
-
-    n, inclined = SYSTEMS[name]
-    obs = system_obs(name)
-    dt, mult, hint = engine.IntegratorConfig().plan_args(system_planets(name))
-    t, rv, er = engine.obs_arrays(obs)
-    return engine.LoglPlan(t, rv, er, obs.Npoints, n, dt, mult, W, period_hint=hint, inclined=inclined,
-                           resolve=(TOL, RMAX)), dt, mult
-
-
-def _run(plan, X):
-    torch = _torch()
-    K = torch.as_tensor(np.ascontiguousarray(np.asarray(X).T), device="cuda")
-    lp, st, _ = plan.logl(K)
-    torch.cuda.synchronize()
-    return lp.cpu().numpy(), st.cpu().numpy()
+    return adaptive_plan(system_planets(name), system_obs(name), W, (TOL, RMAX), SYSTEMS[name][1])
 
 
 def sensitive_cap(n):
@@ -186,23 +159,11 @@ def test_t1_adaptive_systems(name, W):
         assert f2["refined"] == int(rf[clean].sum())
 
 
-def _with_env(env, fn):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _fresh_launch(name, W, X):
-    plan, _, _ = _plan(name, W)
-    got, st = _run(plan, X)
-    return got, st, plan.faults(reset=True)
+def _fresh_launch(name, W, X, env):
+    with switches(env):
+        plan, _, _ = _plan(name, W)
+        got, st = _run(plan, X)
+        return got, st, plan.faults(reset=True)
 
 
 @pytest.mark.parametrize("passes", ["1", "2"])
@@ -213,8 +174,7 @@ def test_eager_halving_passes_bit_identical_systems(name, passes):
     integrating them itself (RVM_EAGER=0)."""
     W = 256
     X = system_walkers(name, W)
-    res = [_with_env({"RVM_EAGER": e, "RVM_EAGER_PASSES": passes}, lambda: _fresh_launch(name, W, X))
-           for e in ("1", "0")]
+    res = [_fresh_launch(name, W, X, {"RVM_EAGER": e, "RVM_EAGER_PASSES": passes}) for e in ("1", "0")]
     np.testing.assert_array_equal(res[0][1], res[1][1])
     np.testing.assert_array_equal(res[0][0], res[1][0])
     assert res[0][2] == res[1][2], (res[0][2], res[1][2])
@@ -230,7 +190,7 @@ def test_refinement_layouts_bit_identical_plain_launch(name):
     X = system_walkers(name, W)
     envs = [{}, {"RVM_REFINE_TEAMS": "2"}, {"RVM_REFINE_TEAMS": "4"}, {"RVM_REFINE_TEAMS": "0"},
             {"RVM_REFINE_SPLIT": "0"}, {"RVM_REFINE_W4": "0"}]
-    runs = [_with_env(env, lambda: _fresh_launch(name, W, X)) for env in envs]
+    runs = [_fresh_launch(name, W, X, env) for env in envs]
     assert runs[0][2]["refined"] > 0 and runs[0][2]["handoff_timeouts"] == 0
     for env, (got, st, f) in zip(envs[1:], runs[1:]):
         np.testing.assert_array_equal(st, runs[0][1], err_msg=str(env))

@@ -10,31 +10,15 @@ import pytest
 
 import oracle as O
 from conftest import S2_PLANETS, S2_SCALES, s2_obs_oracle
+from support import EXTRA_PLANETS, oracle_logl_fn, s2_state_and_obs as _state_and_obs, tight_ball
+from support import torch_or_fail as _torch
 from smala_ref import metric_numpy as _smala_numpy
 
 pytestmark = pytest.mark.gpu
 
 
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available()
-    return torch
-
-
-def _state_and_obs():
-    from rvmcmc import state
-
-    s = state.State(planets=[dict(p) for p in S2_PLANETS])
-    return s, s2_obs_oracle()
-
-
 def _oracle_logl(X, s, obs, dt):
-    """X [W][dim] in the State's free-parameter order -> oracle logL with the kernel algorithm
-    (the State's integrator level sequence)."""
-    pm = s.param_map()
-    P = np.stack([O.kernel_params_to_oracle(pm.vector_to_kernel_np(x)[:, None], 2)[0] for x in X])
-    return O.logl_whx_batch(P, 2, obs, dt, s.integrator.mult)[0]
+    return oracle_logl_fn(s, obs, dt)(X)[0]
 
 
 def numpy_stretch_half(p_s0, lnp_s0, c, u1, u2, u3, lnprob_fn, a=2.0):
@@ -61,8 +45,7 @@ def test_stretch_decisions_match_numpy_emcee():
     s, obs = _state_and_obs()
     W, dim = 128, s.Nvars
     rng = np.random.default_rng(0)
-    scales = np.array([S2_SCALES[k] for k in s.get_rawkeys()])
-    X0 = s.get_params()[None] + 1e-3 * scales * rng.standard_normal((W, dim))
+    X0 = tight_ball(s, (W,), rng)
     ens = EnsembleSampler(W, s, obs, seed=1)
     ens.set_positions(X0)
     ens.compute_lnprob()
@@ -128,8 +111,7 @@ def test_ensemble_reproducible_and_moves():
     s, obs = _state_and_obs()
     W = 256
     rng = np.random.default_rng(1)
-    scales = np.array([S2_SCALES[k] for k in s.get_rawkeys()])
-    X0 = s.get_params()[None] + 1e-3 * scales * rng.standard_normal((W, s.Nvars))
+    X0 = tight_ball(s, (W,), rng)
     runs = []
     for _ in range(2):
         e = EnsembleSampler(W, s, obs, seed=42)
@@ -145,8 +127,6 @@ def test_ensemble_reproducible_and_moves():
 def _large_system(case):
     """Systems of more than 16 free parameters (the stretch kernels' dim > 16 paths): four planar planets, 20; three
     inclined ones, 21."""
-    from test_gpu_logl import EXTRA_PLANETS
-
     planets = [dict(p) for p in S2_PLANETS + EXTRA_PLANETS]
     if case == "three_inclined":
         planets = [dict(p, ix=0.03 * (i + 1), iy=-0.02 * i) for i, p in enumerate(planets[:3])]
@@ -403,8 +383,7 @@ def test_smala_derive_matches_numpy_softabs():
     s, obs = _state_and_obs()
     C_, dim = 24, s.Nvars
     rng = np.random.default_rng(4)
-    scales = np.array([S2_SCALES[k] for k in s.get_rawkeys()])
-    X0 = (s.get_params()[None] + 1e-3 * scales * rng.standard_normal((C_, dim))).T.copy()
+    X0 = tight_ball(s, (C_,), rng).T.copy()
     sm = SmalaChains(s, obs, eps=0.5, alpha=1e3, n_chains=C_, X0=X0, seed=3)
     X = torch.as_tensor(X0, device="cuda")
     lp, g, H, st = fd_logp_grad_metric(sm.state, obs, X, sm.rel_step, sm.pmap, hill_factor=1.0)
@@ -433,8 +412,7 @@ def test_smala_exact_metric_matches_numpy_softabs():
     s, obs = _state_and_obs()
     C_, dim = 12, s.Nvars
     rng = np.random.default_rng(8)
-    scales = np.array([S2_SCALES[k] for k in s.get_rawkeys()])
-    X0 = (s.get_params()[None] + 1e-3 * scales * rng.standard_normal((C_, dim))).T.copy()
+    X0 = tight_ball(s, (C_,), rng).T.copy()
     sm = SmalaChains(s, obs, eps=0.5, alpha=1e3, n_chains=C_, X0=X0, seed=3, hessian="exact")
     lp, g, H, st = sm.state.get_logp_d_dd_batch(obs, torch.as_tensor(X0, device="cuda"), hill_factor=1.0)
     lp, g, H = lp.cpu().numpy(), g.cpu().numpy(), H.cpu().numpy()

@@ -18,30 +18,12 @@ import pytest
 
 import philox_ref
 import smala_ref as R
+from support import rvm_lib as _lib, to_device as _dev, torch_or_fail as _torch
 
 pytestmark = pytest.mark.gpu
 
 EPS = R.EPS
 KEYS = ("lp", "grad", "mu", "L", "G", "logdet", "ok")
-
-
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available()
-    return torch
-
-
-def _lib():
-    _torch()  # first: librvmcmc.so then binds to the HIP runtime torch has loaded, not to a second one
-    from rvmcmc import _lib
-
-    return _lib, _lib.load()
-
-
-def _dev(a, dtype=None):
-    torch = _torch()
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype), device="cuda")
 
 
 def _new_cache(P, n, chains=None):

@@ -7,7 +7,6 @@ appends its largest ratio and the path-class counts to $RVM_STEP_REPORT (JSON li
 profiles/step_unit_tier.jsonl is one run).
 """
 import ctypes as C
-import json
 import math
 import os
 
@@ -16,6 +15,7 @@ import pytest
 from mpmath import mp, mpf
 
 import step_ref as S
+from support import report_line, to_device as _dev
 
 pytestmark = pytest.mark.gpu
 
@@ -30,12 +30,7 @@ SIGNATURES = {
 
 
 def report(what, **kw):
-    path = os.environ.get("RVM_STEP_REPORT")
-    if path:
-        d = {"test": os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0], "what": what}
-        d.update(kw)
-        with open(path, "a") as f:
-            f.write(json.dumps(d) + "\n")
+    report_line("RVM_STEP_REPORT", what, **kw)
 
 
 @pytest.fixture(scope="module")
@@ -57,12 +52,6 @@ def _stream():
     from rvmcmc import _lib
 
     return _lib.stream_handle()
-
-
-def _dev(a, dtype=None):
-    import torch
-
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype), device="cuda")
 
 
 def run_drift(probe, variant, X, enc=None, np_=1):

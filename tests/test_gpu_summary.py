@@ -18,7 +18,8 @@ import numpy as np
 import pytest
 
 import summary_ref as R
-from conftest import S2_PLANETS, S2_SCALES, s2_obs_oracle
+from conftest import S2_SCALES, s2_obs_oracle
+from support import rvm_lib, s2_state, tight_ball, to_device, torch_or_fail as _torch
 
 pytestmark = pytest.mark.gpu
 
@@ -27,29 +28,16 @@ Q16 = np.array([0.0, 1.0, 0.5, 1.0 / 3.0, 0.25, 0.025, 0.16, 0.84, 0.975, 0.999,
 Q_SETS = [np.array([0.0]), np.array([1.0]), np.array([0.5]), np.array([1.0 / 3.0]), np.array([0.25]), Q16]
 
 
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available()
-    return torch
-
-
-def _lib():
-    from rvmcmc import _lib
-
-    return _lib
-
-
 def _dev(a, dtype=np.float64):
-    return _torch().as_tensor(np.array(a, dtype=dtype, order="C"), device="cuda")
+    return to_device(a, dtype, copy=True)
 
 
 def _device_quantiles(ptr, n_rows, row_stride, n_outer, outer_stride, n_inner, q):
     """rvm_rows_quantiles twice on a 0xFF-filled workspace: (out [n_rows][n_q], n_valid [n_rows])."""
     import ctypes as C
 
-    torch, L = _torch(), _lib()
-    lib = L.load()
+    torch = _torch()
+    L, lib = rvm_lib()
     nws = lib.rvm_rows_quantiles_workspace_bytes(n_rows, len(q))
     assert nws > 0 and nws % 8 == 0
     qc = (C.c_double * len(q))(*q)
@@ -195,8 +183,8 @@ SHAPES = [(1, 1, 1, 0), (2, 63, 1, 0), (16, 64, 10, 0), (17, 65, 1, 2), (37, 200
 
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "n%d-W%d-P%d-t%d" % s)
 def test_cov_within_the_derived_bound(shape):
-    torch, L = _torch(), _lib()
-    lib = L.load()
+    torch = _torch()
+    L, lib = rvm_lib()
     n, W, P, t0 = shape
     rng = np.random.default_rng(n * 1000 + W)
     z = rng.standard_normal((t0 + n + 1, P, W))
@@ -243,8 +231,8 @@ def test_cov_within_the_derived_bound(shape):
 @pytest.mark.parametrize("n", [1, 37])
 @pytest.mark.parametrize("S", [1, 64, 65, 300])
 def test_draw_bit_for_bit(S, n, W, t0):
-    torch, L = _torch(), _lib()
-    lib = L.load()
+    torch = _torch()
+    L, lib = rvm_lib()
     P = 3
     rng = np.random.default_rng(S + 10 * n + 100 * W + t0)
     x = rng.standard_normal((t0 + n + 1, P, W))
@@ -283,14 +271,12 @@ _e2e = {}
 def _recorded_ensemble():
     """The S2 system, 20 observations, 64 walkers, 20 recorded steps -- run once, shared, not modified."""
     if not _e2e:
-        from rvmcmc import state
         from rvmcmc.chain import ChainRecorder
         from rvmcmc.ensemble import EnsembleSampler
 
-        s = state.State(planets=[dict(p) for p in S2_PLANETS])
+        s = s2_state()
         obs = s2_obs_oracle(Npoints=20)
-        sc = np.array([S2_SCALES[k] for k in s.get_rawkeys()])
-        X0 = s.get_params() + 1e-3 * sc * np.random.default_rng(11).standard_normal((64, s.Nvars))
+        X0 = tight_ball(s, (64,), 11)
         e = EnsembleSampler(64, s, obs, seed=5)
         e.set_positions(X0)
         rec = ChainRecorder(e, capacity=20)
@@ -390,13 +376,7 @@ def test_predict_end_to_end():
 # ---- predict() on the other three samplers ------------------------------------------------------------------
 
 def _fixed_step_state(**kw):
-    import dataclasses
-
-    from rvmcmc import engine, state
-
-    s = state.State(planets=[dict(p) for p in S2_PLANETS], **kw)
-    s.integrator = dataclasses.replace(engine.DEFAULT_CONFIG, resolve_tol=0.0)  # the fixed-step plan
-    return s
+    return s2_state(fixed_step=True, **kw)
 
 
 def _make_mh():
@@ -409,9 +389,8 @@ def _make_pt():
     from rvmcmc.tempering import PTSampler
 
     s = _fixed_step_state(ignore_params=[["h", "k"], ["h", "k"]])  # 6 free parameters: 16 walkers suffice
-    sc = np.array([S2_SCALES[k] for k in s.get_rawkeys()])
     pt = PTSampler(3, 16, s, s2_obs_oracle(Npoints=20), seed=7)
-    pt.set_positions(s.get_params() + 1e-3 * sc * np.random.default_rng(13).standard_normal((3, 16, s.Nvars)))
+    pt.set_positions(tight_ball(s, (3, 16), 13))
     return pt
 
 

@@ -6,37 +6,15 @@ Bit-exact tests use the fixed-step plan (resolve_tol = 0), whose T1 twin is the 
 logl_whx_batch.  tests/test_tempering_cpu.py runs the full-step input through the restatement with
 the oracle alone and asserts that no decision is near a tie: the comparisons here have no exemptions.
 """
-import dataclasses
-
 import numpy as np
 import pytest
 
 import oracle as O
 import philox_ref
 import pt_ref
-from conftest import S2_PLANETS, S2_SCALES, s2_obs_oracle
+from support import s2_state_and_obs as _state_and_obs, state_scales as _scales, tight_ball, torch_or_fail as _torch
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available()
-    return torch
-
-
-def _state_and_obs(fixed_step):
-    from rvmcmc import engine, state
-
-    s = state.State(planets=[dict(p) for p in S2_PLANETS])
-    if fixed_step:
-        s.integrator = dataclasses.replace(engine.DEFAULT_CONFIG, resolve_tol=0.0)
-    return s, s2_obs_oracle()
-
-
-def _scales(s):
-    return np.array([S2_SCALES[k] for k in s.get_rawkeys()])
 
 
 # ---- 1. the swap kernel alone ---------------------------------------------------------------------
@@ -172,7 +150,7 @@ def test_one_temperature_is_the_ensemble_sampler():
     s, obs = _state_and_obs(fixed_step=True)
     W = 64
     rng = np.random.default_rng(4)
-    X0 = s.get_params()[None] + 1e-2 * _scales(s) * rng.standard_normal((W, s.Nvars))
+    X0 = tight_ball(s, (W,), rng, 1e-2)
     ens = EnsembleSampler(W, s, obs, seed=7)
     ens.fused = False
     ens.set_positions(X0)

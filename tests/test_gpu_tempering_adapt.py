@@ -9,38 +9,20 @@ tests/test_tempering_adapt_cpu.py runs the full-iteration input through the rest
 oracle alone and asserts that no decision is near a tie (margins 3.4e-4 and 2.5e-2, against the
 ~1e-11 a beta error of 1e-12 moves a decision statistic): the comparisons here have no exemptions.
 """
-import dataclasses
-
 import numpy as np
 import pytest
 
 import pt_adapt_ref as R
 import pt_ref
-from conftest import S2_PLANETS, S2_SCALES, s2_obs_oracle
-from test_tempering_adapt_cpu import CASE
+from support import PT_ADAPT_CASE as CASE, s2_state_and_obs, state_scales as _scales, torch_or_fail as _torch
 
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-12
 
 
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available()
-    return torch
-
-
 def _state_and_obs():
-    from rvmcmc import engine, state
-
-    s = state.State(planets=[dict(p) for p in S2_PLANETS])
-    s.integrator = dataclasses.replace(engine.DEFAULT_CONFIG, resolve_tol=0.0)  # the fixed-step plan
-    return s, s2_obs_oracle()
-
-
-def _scales(s):
-    return np.array([S2_SCALES[k] for k in s.get_rawkeys()])
+    return s2_state_and_obs(fixed_step=True)
 
 
 # ---- 1. the update alone ----------------------------------------------------------------------------

@@ -3,15 +3,9 @@ knob as read_plan_knobs parses it, the wait's safety bound against team B's own 
 below spin_ticks << 1 for every hand-off timeout, the 10 ns one of tests/test_gpu_resolve.py included), and the
 layouts grown for it (rq_tb right behind rq_tf, the wait's counters behind the mark words of hw).  rvm_plan_host.cpp is
 built with the host compiler and a small driver, as csrc/host_sanitize.cpp does."""
-import json
-import os
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rvel-mcmc_amd", "csrc")
+from support import host_driver_report
 
 DRIVER = r"""
 #include <cstdio>
@@ -83,20 +77,7 @@ int main() {
 
 @pytest.fixture(scope="module")
 def report(tmp_path_factory):
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    d = tmp_path_factory.mktemp("hedge_wait_host")
-    src = d / "driver.cpp"
-    src.write_text(DRIVER)
-    exe = d / "driver"
-    b = subprocess.run([cxx, "-std=c++17", "-O1", "-I", CSRC, "-o", str(exe), str(src),
-                        os.path.join(CSRC, "rvm_plan_host.cpp")], capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stderr[-3000:]
-    env = {k: v for k, v in os.environ.items() if not k.startswith("RVM_")}
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120, env=env)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return json.loads(r.stdout)
+    return host_driver_report(tmp_path_factory, "hedge_wait_host", DRIVER)
 
 
 def test_knob_parses(report):

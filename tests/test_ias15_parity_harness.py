@@ -6,20 +6,18 @@ import numpy as np
 
 import ias15_parity as IP
 import oracle as O
-from conftest import S2_PLANETS, S2_SCALES, s2_obs_oracle
+from conftest import S2_PLANETS, s2_obs_oracle
 from philox_ref import stretch_uniforms
+from support import oracle_params, s2_rows_and_scales, s2_state, steady_ensemble, tight_ball
 
 
 def test_stretch_harness_whx_vs_ias15():
-    from rvmcmc.state import State
-
-    s = State(planets=[dict(p) for p in S2_PLANETS])
+    s = s2_state()
     pm = s.param_map()
     obs = s2_obs_oracle()
     dt, mult, _ = s.integrator.plan_args(s.planets)
     W, dim, n = 64, s.Nvars, 32
-    scales = np.array([S2_SCALES[k] for k in s.get_rawkeys()])
-    X = s.get_params()[None] + 1e-3 * scales * np.random.default_rng(0).standard_normal((W, dim))
+    X = tight_ball(s, (W,), 0)
     pos = [X[:n].copy(), X[n:].copy()]
     lw = [O.logl_whx_batch(IP.to_oracle(pm, p), 2, obs, dt, mult)[0] for p in pos]
     li = [IP.ias15_logl(IP.to_oracle(pm, p), 2, obs)[0] for p in pos]
@@ -75,14 +73,12 @@ def test_adaptive_resolution_keeps_t2_on_a_wide_ball():
 
     obs = s2_obs_oracle()
     dt, mult, _ = engine.IntegratorConfig().plan_args(S2_PLANETS)
-    x0 = np.array([p[k] for p in S2_PLANETS for k in "mahkl"])
-    sc = np.array([S2_SCALES[k] for _ in S2_PLANETS for k in "mahkl"])
+    x0, sc = s2_rows_and_scales()
     rng = np.random.default_rng(3)
     X = x0 + 0.6 * sc * rng.standard_normal((48, 10))
     j, z = rng.integers(0, 48, 48), (rng.random(48) + 1.0) ** 2 / 2.0
     X = np.concatenate([X, X[j] - z[:, None] * (X[j] - X)])
-    P = np.zeros((len(X), 2, 7))
-    P[:, :, :5] = X.reshape(-1, 2, 5)
+    P = oracle_params(X, 2)
     la, sa, rf, _, _ = O.logl_whx_adapt_batch(P, 2, obs, dt, mult, 5e-7, 4)
     l0, s0 = O.logl_whx_batch(P, 2, obs, dt, mult)
     li, si = IP.ias15_logl(P, 2, obs)
@@ -102,12 +98,9 @@ def test_joint_certain_reject_at_the_steady_state():
     lower bounds in the certain-reject test no proposal needs more than one halving pass, no cut
     proposal is one IAS15 would accept, nothing is left UNRESOLVED, and every uncut OK proposal is
     within T2 of IAS15."""
-    import os
-
-    from conftest import ROOT
     from rvmcmc import engine
 
-    E = np.load(os.path.join(ROOT, "scripts", "probe", "ens_it2000.npy"))
+    E = steady_ensemble("s2")
     obs = s2_obs_oracle()
     n = 192
     X, C = E[:n], E[2048:2048 + n]
@@ -118,9 +111,7 @@ def test_joint_certain_reject_at_the_steady_state():
     Q = C[j] - z[:, None] * (C[j] - X)
 
     def rows(A):
-        P = np.zeros((len(A), 2, 7))
-        P[:, :, :5] = A.reshape(-1, 2, 5)
-        return P
+        return oracle_params(A, 2)
 
     cfg = engine.IntegratorConfig()
     dt, mult, _ = cfg.plan_args(S2_PLANETS)
@@ -165,9 +156,7 @@ def _cut_case(system, n):
     Q = C[j] - z[:, None] * (C[j] - X)
 
     def rows(A):
-        P = np.zeros((len(A), npl, 7))
-        P[:, :, :5] = A.reshape(-1, npl, 5)
-        return P
+        return oracle_params(A, npl)
 
     cfg = engine.IntegratorConfig()
     dt, mult, _ = cfg.plan_args(planets)

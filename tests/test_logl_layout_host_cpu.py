@@ -4,15 +4,9 @@ the layouts' comments state, every range of it lies inside without overlap, and 
 invariants; and the layout of every shape the GPU tests name (tests/test_gpu_logl.py, and the adaptive plans of
 tests/test_gpu_resolve_systems.py) is pinned, each value derived from the rule.  rvm_plan_host.cpp is built with the host compiler and a small driver, as
 tests/test_hedge_wait_host_cpu.py does."""
-import json
-import os
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rvel-mcmc_amd", "csrc")
+from support import host_driver_report
 
 DRIVER = r"""
 #include <algorithm>
@@ -140,20 +134,7 @@ int main() {
 
 @pytest.fixture(scope="module")
 def report(tmp_path_factory):
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    d = tmp_path_factory.mktemp("logl_layout_host")
-    src = d / "driver.cpp"
-    src.write_text(DRIVER)
-    exe = d / "driver"
-    b = subprocess.run([cxx, "-std=c++17", "-O1", "-I", CSRC, "-o", str(exe), str(src),
-                        os.path.join(CSRC, "rvm_plan_host.cpp")], capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stderr[-3000:]
-    env = {k: v for k, v in os.environ.items() if not k.startswith("RVM_")}
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120, env=env)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return json.loads(r.stdout)
+    return host_driver_report(tmp_path_factory, "logl_layout_host", DRIVER)
 
 
 def test_request_is_the_lds_layouts_total(report):

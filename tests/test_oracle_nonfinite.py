@@ -7,7 +7,7 @@ import numpy as np
 
 import oracle as O
 from conftest import S2_PLANETS, s2_obs_oracle
-from test_gpu_contract import NONFINITE_WALKERS
+from support import NONFINITE_WALKERS
 
 
 def test_nonfinite_halving_pass_ends_the_walker_on_the_oracle():

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import summary_ref as R
+from support import refusal_text as _err
 from rvmcmc import _lib
 
 U = 2.0 ** -53
@@ -100,11 +101,6 @@ def test_draw_restatement():
 
 
 # ---- argument errors: < 0 before any HIP call, the argument named ---------------------------------------
-
-def _err(rc):
-    assert rc < 0
-    return _lib.load().rvm_last_error()
-
 
 def _q(*v):
     return (C.c_double * len(v))(*v)

@@ -2,21 +2,17 @@
 point's refusals, the numpy restatement's edge cases (tests/pt_adapt_ref.py), and the input of
 tests/test_gpu_tempering_adapt.py run through the restatement with the oracle as the likelihood."""
 import ctypes as C
-import dataclasses
 
 import numpy as np
 import pytest
 
-import oracle as O
 import pt_adapt_ref as R
 import pt_ref
-from conftest import S2_PLANETS, S2_SCALES, s2_obs_oracle
+from conftest import S2_PLANETS, s2_obs_oracle
+from support import PT_ADAPT_CASE as CASE, oracle_logl_fn as _oracle_fn, s2_state_and_obs, state_scales
 
-from rvmcmc import _lib, engine, state
+from rvmcmc import _lib, state
 from rvmcmc.tempering import PTSampler, default_betas, log_evidence_ratio
-
-# the full-iteration case shared with tests/test_gpu_tempering_adapt.py
-CASE = dict(T=4, W=24, iters=4, seed=0, lag=10.0, time=2.0)
 
 
 # ---- 1. refusals without a device -----------------------------------------------------------------
@@ -156,27 +152,14 @@ def test_restatement_moments_and_evidence():
 
 # ---- 3. the GPU test's input through the restatement, the oracle as likelihood --------------------
 
-def _oracle_fn(s, obs, dt):
-    pm = s.param_map()
-
-    def fn(X):
-        P = np.stack([O.kernel_params_to_oracle(pm.vector_to_kernel_np(x)[:, None], 2)[0] for x in X])
-        return O.logl_whx_batch(P, 2, obs, dt, s.integrator.mult)
-
-    return fn
-
-
 def test_restatement_adapts_on_the_gpu_tests_input():
     """The input of test_gpu_tempering_adapt.py's full iterations (S2, fixed-step plan, T = 4, W = 24,
     rng 0, 4 iterations, default ladder, lag 10, time 2, an update after every sweep) through the
     restatement with the oracle as the likelihood: every walker evaluates cleanly, no decision is near
     a tie, no update is refused, the interior betas move and the end betas do not."""
-    s = state.State(planets=[dict(p) for p in S2_PLANETS])
-    s.integrator = dataclasses.replace(engine.DEFAULT_CONFIG, resolve_tol=0.0)
-    obs = s2_obs_oracle()
+    s, obs = s2_state_and_obs(fixed_step=True)
     T, W, iters = CASE["T"], CASE["W"], CASE["iters"]
-    scales = np.array([S2_SCALES[k] for k in s.get_rawkeys()])
-    X, draws = pt_ref.case_inputs(s.get_params(), scales, T, W, iters, seed=CASE["seed"])
+    X, draws = pt_ref.case_inputs(s.get_params(), state_scales(s), T, W, iters, seed=CASE["seed"])
     dt = s.integrator.plan_args(s.planets)[0]
     betas0 = default_betas(T, s.Nvars)
     lad = pt_ref.Ladder(X, betas0, _oracle_fn(s, obs, dt))

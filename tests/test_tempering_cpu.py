@@ -2,17 +2,16 @@
 checks, the entry points' argument checks, and the numpy restatement (tests/pt_ref.py) run with the
 oracle as the likelihood on the input tests/test_gpu_tempering.py compares the device against."""
 import ctypes as C
-import dataclasses
 import math
 
 import numpy as np
 import pytest
 
-import oracle as O
 import pt_ref
-from conftest import S2_PLANETS, S2_SCALES, s2_obs_oracle
+from conftest import S2_PLANETS, s2_obs_oracle
+from support import oracle_logl_fn as _oracle_fn, s2_state_and_obs, state_scales
 
-from rvmcmc import _lib, engine, state
+from rvmcmc import _lib, state
 from rvmcmc.tempering import PTSampler, default_betas
 
 
@@ -93,28 +92,15 @@ def test_entry_points_refuse_bad_arguments_without_a_device():
     assert lib.rvm_pt_swap(10, 1, 4, None, None, None, None, None, 0, 0, None, None, None) == 0
 
 
-def _oracle_fn(s, obs, dt):
-    pm = s.param_map()
-
-    def fn(X):
-        P = np.stack([O.kernel_params_to_oracle(pm.vector_to_kernel_np(x)[:, None], 2)[0] for x in X])
-        return O.logl_whx_batch(P, 2, obs, dt, s.integrator.mult)
-
-    return fn
-
-
 def test_restatement_is_self_consistent_on_the_gpu_tests_input():
     """The input of test_gpu_tempering.py::test_full_steps_match_numpy (S2, T = 3, W = 24, rng 0, 3
     iterations) through the restatement with the oracle (the fixed-step plan's T1 twin) as the
     likelihood: every walker evaluates cleanly, no decision is near a tie, tempering changes
     decisions, and every pair both exchanges and keeps walkers -- so the GPU comparison can fail on a
     wrong beta, a wrong pairing or a swap that forgets lnp, and needs no exemptions."""
-    s = state.State(planets=[dict(p) for p in S2_PLANETS])
-    s.integrator = dataclasses.replace(engine.DEFAULT_CONFIG, resolve_tol=0.0)
-    obs = s2_obs_oracle()
+    s, obs = s2_state_and_obs(fixed_step=True)
     T, W, iters = 3, 24, 3
-    scales = np.array([S2_SCALES[k] for k in s.get_rawkeys()])
-    X, draws = pt_ref.case_inputs(s.get_params(), scales, T, W, iters, seed=0)
+    X, draws = pt_ref.case_inputs(s.get_params(), state_scales(s), T, W, iters, seed=0)
     dt = s.integrator.plan_args(s.planets)[0]
     betas = default_betas(T, s.Nvars)
     lad = pt_ref.Ladder(X, betas, _oracle_fn(s, obs, dt))

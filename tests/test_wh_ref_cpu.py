@@ -46,14 +46,15 @@ def test_fixture_holds_the_case_table():
     for n, c in CASES.items():
         assert {k: FX[n][k] for k in c} == c, n
         assert len(FX[n]["walkers_out"]) == len(c["walkers"])
+    import support
     import test_gpu_derivs
     import test_gpu_logl
     from conftest import S2_PLANETS
 
-    assert R.FLOOR == test_gpu_derivs.FLOOR and R.FLOOR_FACTOR == test_gpu_logl.T1_SENS_FACTOR
-    assert R.S2_PLANETS == S2_PLANETS and R.EXTRA_PLANETS == test_gpu_logl.EXTRA_PLANETS
+    assert R.FLOOR == test_gpu_derivs.FLOOR and R.FLOOR_FACTOR == support.T1_SENS_FACTOR
+    assert R.S2_PLANETS == S2_PLANETS and R.EXTRA_PLANETS == support.EXTRA_PLANETS
     assert R.S2_INCLINED == test_gpu_logl.S2_INCLINED
-    assert R._ball(R.pal_rows(S2_PLANETS), 2, 1e-3, 0) == test_gpu_logl._ball(S2_PLANETS, 2, 1e-3, 0).tolist()
+    assert R._ball(R.pal_rows(S2_PLANETS), 2, 1e-3, 0) == support.pal_ball(S2_PLANETS, 2, 1e-3, 0).tolist()
 
 
 def test_mpf_restatement_matches_the_oracle(mpf_runs):
