@@ -1169,7 +1169,8 @@ __device__ __forceinline__ u32x4 philox(u32x4 c, uint32_t k0, uint32_t k1) {
     return c;
 }
 
-// two uniforms in the open interval (0, 1), 53-bit resolution
+// two uniforms in (0, 1], 53-bit resolution: the top value ((2^53 - 1) + 0.5) 2^-53 rounds to exactly 1.0
+// (log(1.0) = 0 is harmless to the accept tests; an index floor(u n) must be clamped, as stretch_zj does)
 __device__ __forceinline__ void uniform2(uint64_t seed, uint64_t item, uint64_t iteration, uint32_t stream, double& u0,
                                          double& u1) {
     const u32x4 c{(uint32_t)item, (uint32_t)(item >> 32), (uint32_t)iteration,

@@ -17,7 +17,8 @@ enum : uint32_t {
     RNG_CHAIN_DRAW = 8,  // (rvm_summary.hip)
 };
 
-// z = ((a - 1) u1 + 1)^2 / a  and  j = floor(u2 n1) (emcee _propose_stretch)
+// z = ((a - 1) u1 + 1)^2 / a  and  j = floor(u2 n1) (emcee _propose_stretch).  uniform2 can return
+// exactly 1.0, where floor(u2 n1) = n1: the clamp is what keeps that draw inside the complement.
 __device__ __forceinline__ void stretch_zj(double u1, double u2, double a, int n1, double& z, int& j) {
 #pragma clang fp contract(off)
     z = ((a - 1.0) * u1 + 1.0) * ((a - 1.0) * u1 + 1.0) / a;

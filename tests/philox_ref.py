@@ -1,8 +1,9 @@
 """Plain-Python restatement of the device RNG (rvm_device.h: philox / uniform2).
 
 Philox4x32-10 (Salmon et al., SC'11) keyed by the 64-bit seed, counter
-(item lo, item hi, iteration lo, (iteration hi & 0xFFFF) | stream << 16); two uniforms in (0, 1)
-with 53-bit resolution: ((x >> 5) * 2^26 + (y >> 6) + 0.5) / 2^53.
+(item lo, item hi, iteration lo, (iteration hi & 0xFFFF) | stream << 16); two uniforms in (0, 1]
+with 53-bit resolution: ((x >> 5) * 2^26 + (y >> 6) + 0.5) / 2^53.  The interval is closed at the top:
+the largest value, ((2^53 - 1) + 0.5) / 2^53, rounds to exactly 1.0.
 """
 import numpy as np
 
