@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define RVM_ABI_VERSION 12
+#define RVM_ABI_VERSION 13
 
 /* per-walker status codes (status_out) */
 #define RVM_STATUS_OK 0
@@ -579,6 +579,51 @@ int rvm_chain_cov(const double* chain, int32_t n_params, int32_t n_cols, int64_t
 int rvm_chain_draw(const double* chain, int32_t n_params, int32_t n_cols, int64_t t0, int64_t t1, int32_t n_samples,
                    uint64_t seed, uint64_t draw_id, const double* draws, double* x_out, int64_t* idx_out,
                    void* stream);
+
+/* ---- periodograms of data already in device memory -------------------------------------------------
+ * The generalised Lomb-Scargle periodogram (Zechmeister & Kuerster 2009: weights, floating mean) of
+ * n_series residual series y_s = data - model[:, s] at the frequencies f_k, over n_obs epochs: which
+ * periods are in the velocities, and what a fit left in them.  The conventions of the summary entry
+ * points hold: device pointers, no allocation, no synchronisation, stream-ordered and capturable, no
+ * floating-point atomics, the same bits from run to run; argument errors return < 0 before any HIP call
+ * and name the argument in rvm_last_error; a workspace's contents are unspecified before and after a call.
+ *
+ *   tau [n_obs]: epochs less a reference time of the caller's.  w [n_obs]: weights that sum to 1 up to
+ *   rounding (the caller normalises 1 / sigma^2; used as given).  data [n_obs].  model, nullable:
+ *   [n_obs][model_ld], series s in column s -- the layout of rv_out.  power_out[k power_ld + s]: rows are
+ *   frequencies, so one rvm_rows_quantiles call over [n_freq][n_series] gives a band per frequency.
+ *   freq_out [n_freq], nullable.  cos_out, sin_out [n_freq][n_obs].
+ *   Limits: n_obs 1 .. 2 RVM_MAX_EPOCHS_PER_DIRECTION; n_freq >= 1; n_series >= 1; k0 >= 0 and
+ *   k0 + n_freq <= 2^53; f0, df finite; model_ld >= n_series when model is given; power_ld >= n_series;
+ *   float_mean 0 or 1; workspace 16-byte aligned.
+ *
+ * The definition is the algorithm: every product and sum below is one IEEE double operation, fma only
+ * where it is written, and every sum runs over i ascending in one thread from acc = 0.
+ *   1. basis, frequency index k < n_freq and epoch i:  f_k = fma((double)(k0 + k), df, f0);  x = f_k tau_i;
+ *      r = x - rint(x) (exact);  (s_ki, c_ki) = sincospi(2 r), the device library's;  freq_out[k] = f_k.
+ *      The phase is reduced in cycles before the trigonometry: its only error is the one rounding of x.
+ *   2. per frequency:  C = sum fma(w_i, c_i, acc), S likewise (float_mean = 0: C = S = 0);
+ *      ct_i = c_i - C, st_i = s_i - S;  u_i = w_i ct_i, v_i = w_i st_i;
+ *      CC = sum fma(u_i, ct_i, acc), SS = sum fma(v_i, st_i, acc), CS = sum fma(u_i, st_i, acc).
+ *   3. per series:  y_i = data_i - model[i][s] (data_i without a model);  m = sum fma(w_i, y_i, acc)
+ *      (float_mean = 0: m = 0);  z_i = y_i - m;  YY = sum fma(w_i z_i, z_i, acc).
+ *   4. per (k, s):  YC = sum fma(u_ki, z_is, acc), YS = sum fma(v_ki, z_is, acc);  D = CC SS - CS CS;
+ *      p = ((SS YC) YC + (CC YS) YS - (2 (CS YC)) YS) / (YY D), left to right.
+ *      Whatever IEEE gives is the result: a NaN column of model gives NaN powers in that column (which
+ *      rvm_rows_quantiles does not count), YY = 0 gives NaN.  With a floating mean and n_obs = 3 the fit is
+ *      exact and D is rounding noise: the caller keeps n_obs >= 4 (>= 3 without).
+ * gls_basis writes step 1.  gls_power fills its table by launching the same kernel, so the public basis is
+ * what the power used, and runs the frequencies in chunks (a table of about 64 MiB) that the result does
+ * not depend on: a call over [k0, k0 + n_freq) equals the concatenation of calls over its pieces, bit for
+ * bit.  workspace: rvm_gls_workspace_bytes(n_obs, n_freq, n_series) bytes (0 on bad arguments): a chunk's
+ * u, v table and per-frequency sums, the per-series YY and z. */
+int rvm_gls_basis(const double* tau, int32_t n_obs, double f0, double df, int64_t k0, int32_t n_freq, double* cos_out,
+                  double* sin_out, double* freq_out, void* stream);
+size_t rvm_gls_workspace_bytes(int32_t n_obs, int32_t n_freq, int32_t n_series);
+int rvm_gls_power(const double* tau, const double* w, int32_t n_obs, const double* data, const double* model,
+                  int64_t model_ld, int32_t n_series, double f0, double df, int64_t k0, int32_t n_freq,
+                  int32_t float_mean, double* power_out, int64_t power_ld, double* freq_out, void* workspace,
+                  void* stream);
 
 const char* rvm_last_error(void);
 int rvm_abi_version(void);

@@ -462,6 +462,59 @@ int rvm_chain_draw(const double* chain, int32_t n_params, int32_t n_cols, int64_
                                           idx_out, (hipStream_t)stream));
 }
 
+// ---- periodograms (rvm_gls.hip) ----
+// the frequency grid f0 + (k0 + k) df, k < n_freq: the refusal's text, or null
+static const char* gls_bad_grid(double f0, double df, int64_t k0, int32_t n_freq) {
+    if (n_freq < 1) return "n_freq must be >= 1";
+    if (k0 < 0) return "k0 must be >= 0";
+    if (k0 > ((int64_t)1 << 53) - n_freq) return "k0 + n_freq must be <= 2^53";
+    if (!std::isfinite(f0)) return "f0 must be finite";
+    if (!std::isfinite(df)) return "df must be finite";
+    return nullptr;
+}
+static const char* gls_bad_n_obs(int32_t n_obs) {
+    return n_obs < 1 || n_obs > 2 * RVM_MAX_EPOCHS_PER_DIRECTION ? "n_obs must be 1 .. 3400" : nullptr;
+}
+
+int rvm_gls_basis(const double* tau, int32_t n_obs, double f0, double df, int64_t k0, int32_t n_freq, double* cos_out,
+                  double* sin_out, double* freq_out, void* stream) {
+    const Entry at{"rvm_gls_basis"};
+    if (!tau) return at.null("tau");
+    if (const char* m = gls_bad_n_obs(n_obs)) return at.bad(m);
+    if (const char* m = gls_bad_grid(f0, df, k0, n_freq)) return at.bad(m);
+    if (!cos_out) return at.null("cos_out");
+    if (!sin_out) return at.null("sin_out");
+    return at.done(rvm::launch_gls_basis(tau, n_obs, n_obs, f0, df, k0, n_freq, cos_out, sin_out, freq_out,
+                                         (hipStream_t)stream));
+}
+
+size_t rvm_gls_workspace_bytes(int32_t n_obs, int32_t n_freq, int32_t n_series) {
+    if (gls_bad_n_obs(n_obs) || n_freq < 1 || n_series < 1) return 0;
+    return rvm::gls_workspace_bytes(n_obs, n_freq, n_series);
+}
+
+int rvm_gls_power(const double* tau, const double* w, int32_t n_obs, const double* data, const double* model,
+                  int64_t model_ld, int32_t n_series, double f0, double df, int64_t k0, int32_t n_freq,
+                  int32_t float_mean, double* power_out, int64_t power_ld, double* freq_out, void* workspace,
+                  void* stream) {
+    const Entry at{"rvm_gls_power"};
+    if (!tau) return at.null("tau");
+    if (!w) return at.null("w");
+    if (const char* m = gls_bad_n_obs(n_obs)) return at.bad(m);
+    if (!data) return at.null("data");
+    if (n_series < 1) return at.bad("n_series must be >= 1");
+    if (model && model_ld < n_series) return at.bad("model_ld must be >= n_series");
+    if (const char* m = gls_bad_grid(f0, df, k0, n_freq)) return at.bad(m);
+    if (float_mean != 0 && float_mean != 1) return at.bad("float_mean must be 0 or 1");
+    if (!power_out) return at.null("power_out");
+    if (power_ld < n_series) return at.bad("power_ld must be >= n_series");
+    if (!workspace) return at.null("workspace");
+    if ((uintptr_t)workspace % 16 != 0) return at.bad("workspace must be 16-byte aligned");
+    return at.done(rvm::launch_gls_power(tau, w, n_obs, data, model, model_ld, n_series, f0, df, k0, n_freq,
+                                         float_mean, power_out, power_ld, freq_out, (double*)workspace,
+                                         (hipStream_t)stream));
+}
+
 int rvm_mh_propose(int32_t n_params, int32_t n_chains, int64_t chain_begin, const double* x, const double* scales,
                    double step_size, uint64_t seed, uint64_t iteration, const double* draws, double* q_out,
                    void* stream) {

@@ -85,6 +85,13 @@ hipError_t launch_chain_cov(const double* x, int P, int W, int64_t t0, int64_t t
                             double* part, hipStream_t st);
 hipError_t launch_chain_draw(const double* x, int P, int W, int64_t t0, int64_t t1, int S, uint64_t seed,
                              uint64_t draw_id, const double* draws, double* xo, int64_t* idx, hipStream_t st);
+int64_t gls_chunk_freqs(int N);
+size_t gls_workspace_bytes(int N, int F, int S);
+hipError_t launch_gls_basis(const double* tau, int N, int64_t ld, double f0, double df, int64_t k0, int F,
+                            double* cos_out, double* sin_out, double* freq_out, hipStream_t st);
+hipError_t launch_gls_power(const double* tau, const double* w, int N, const double* data, const double* model,
+                            int64_t model_ld, int S, double f0, double df, int64_t k0, int F, int float_mean,
+                            double* power, int64_t power_ld, double* freq_out, double* ws, hipStream_t st);
 hipError_t launch_fd_params(int P, int n, const double* x, double rel, const double* fl, double* out, hipStream_t st);
 hipError_t launch_smala_derive(int P, int C, int E, const double* x, double rel, const double* fl,
                                const double* lp_st, const int32_t* st_st, const double* rv, const double* w,

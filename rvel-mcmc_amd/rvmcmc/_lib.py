@@ -23,7 +23,7 @@ RVM_MAX_LEVELS = 6
 RVM_MAX_EPOCHS_PER_DIRECTION = 1700  # epochs with t >= 0, and with t < 0, per plan
 RVM_MAX_QUANTILES = 16  # rvm_rows_quantiles
 RVM_N_COUNTERS = 7  # rvm_plan_counters
-ABI_VERSION = 12  # include/rvmcmc.h RVM_ABI_VERSION
+ABI_VERSION = 13  # include/rvmcmc.h RVM_ABI_VERSION
 
 
 class RvmConfig(C.Structure):
@@ -147,6 +147,10 @@ SIGNATURES = {
     "rvm_chain_cov": (C.c_int, [_dp, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _dp, _dp, _dp, _dp]),
     "rvm_chain_draw": (C.c_int, [_dp, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
                                  _dp, _dp, _dp, _dp]),
+    "rvm_gls_basis": (C.c_int, [_dp, C.c_int32, C.c_double, C.c_double, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp]),
+    "rvm_gls_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "rvm_gls_power": (C.c_int, [_dp, _dp, C.c_int32, _dp, _dp, C.c_int64, C.c_int32, C.c_double, C.c_double,
+                                C.c_int64, C.c_int32, C.c_int32, _dp, C.c_int64, _dp, _dp, _dp]),
     "rvm_fd_params": (C.c_int, [C.c_int32, C.c_int32, _dp, C.c_double, _dp, _dp, _dp]),
     "rvm_logl_derivs_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rvm_logl_derivs": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int32, C.POINTER(C.c_int32), C.c_double, _dp, _dp,

@@ -31,6 +31,10 @@ RV curves over the data and reports the parameters' distribution) is read from t
                 and on the rows of the likelihood launch's rv_out matrix
     cov         rvm_chain_cov around the mean of rvm_chain_moments, rvm_chain_autocov's summation order
     draw        rvm_chain_draw: Philox keyed by (seed, sample, draw_id), with replacement
+
+and what the posterior's fits leave in the data (rvm_gls.hip, rvmcmc/periodogram.py):
+
+    pb = rec.residual_periodogram(n_samples=1024, discard=1000)   # pb.bands [n_q][F] at pb.freq, pb.data_power
 """
 from __future__ import annotations
 
@@ -373,6 +377,14 @@ class ChainRecorder:
                                                _lib.stream_handle()), "rvm_chain_draw")
         return X, idx
 
+    def _samples(self, X):
+        """The caller's samples [P][S] as predict() and residual_periodogram() take them, contiguous."""
+        torch = _torch()
+        if (not torch.is_tensor(X) or X.dtype != torch.float64 or X.dim() != 2 or X.shape[0] != self.n_params
+                or X.shape[1] < 1 or X.device != self._chain.device):
+            raise ValueError("samples must be a float64 tensor [n_params][S] on the recorder's device")
+        return X.contiguous()
+
     def predict(self, times, n_samples=1024, discard=0, q=DEFAULT_Q, seed=0, samples=None, return_samples=False):
         """RvBands: the quantiles q of the model RV at `times` over n_samples states drawn from the recorded
         steps [discard, n) (or over the caller's samples [P][S], a device tensor of free-parameter vectors)
@@ -400,11 +412,7 @@ class ChainRecorder:
         if samples is None:
             X, idx = self.draw(n_samples, discard, seed)
         else:
-            X = samples
-            if (not torch.is_tensor(X) or X.dtype != torch.float64 or X.dim() != 2 or X.shape[0] != self.n_params
-                    or X.shape[1] < 1 or X.device != self._chain.device):
-                raise ValueError("samples must be a float64 tensor [n_params][S] on the recorder's device")
-            X = X.contiguous()
+            X = self._samples(samples)
         key = times.tobytes()
         if self._epochs is None or self._epochs[0] != key:
             self._epochs = (key, Epochs(times))  # (keeps the plan plan_for caches on it)
@@ -418,6 +426,52 @@ class ChainRecorder:
         out = RvBands(times=times, q=q, bands=np.ascontiguousarray(bands.T), n_valid=n_valid)
         if return_samples:
             out.X, out.idx, out.status, out.rv = X, idx, status, rv
+        return out
+
+    def residual_periodogram(self, grid=None, n_samples=1024, discard=0, q=DEFAULT_Q, seed=0, samples=None,
+                             float_mean=True, return_samples=False):
+        """PeriodogramBands: the quantiles q, per frequency, of the generalised Lomb-Scargle power of the
+        residuals (observed RV - model RV) over n_samples states drawn from the recorded steps [discard, n)
+        (or over the caller's samples [P][S]) -- what the posterior's fits leave in the data.  One likelihood
+        launch with rv_out on the sampler's own observation set (state, parameter map and Hill factor as in
+        predict()), the columns that are not RVM_STATUS_OK masked to NaN, rvm_gls_power with that matrix as
+        the model, then rvm_rows_quantiles over the [F][S] rows; data_power is the data's own periodogram on
+        the same grid.  grid: (f0, df, n_freq), default periodogram.freq_grid of the epochs.  Synchronises
+        for the [n_q][F], [F] and [F] results."""
+        from . import engine, periodogram
+
+        torch = _torch()
+        sampler = self.sampler
+        state, obs = getattr(sampler, "state", None), getattr(sampler, "obs", None)
+        if state is None or obs is None or not hasattr(sampler, "pmap"):
+            raise TypeError(f"{type(sampler).__name__} has no obs / state / pmap: nothing to take residuals from")
+        t, rvobs, er = engine.obs_arrays(obs)
+        tau, w = periodogram.series_inputs(t, er, float_mean)
+        grid = periodogram._grid(grid, t)
+        q = _q_array(q)
+        idx = None
+        if samples is None:
+            X, idx = self.draw(n_samples, discard, seed)
+        else:
+            X = self._samples(samples)
+        hf = getattr(sampler, "hill_factor", state.hillRadiusFactor)
+        F = grid[2]
+        with torch.cuda.device(self.device):
+            _, status, rv = state.get_logp_batch(obs, X, hill_factor=hf, want_rv=True, pmap=sampler.pmap)
+            masked = torch.where((status == _lib.RVM_STATUS_OK)[None, :], rv, torch.full_like(rv, float("nan")))
+            S = int(X.shape[1])
+            dev = [torch.as_tensor(np.ascontiguousarray(a), device=self.device) for a in (tau, w, rvobs)]
+            power, freq = periodogram.power_on_device(self.lib, dev[0], dev[1], dev[2], masked.contiguous(), S, grid,
+                                                      float_mean, self.device)
+            data_power, _ = periodogram.power_on_device(self.lib, dev[0], dev[1], dev[2], None, 1, grid, float_mean,
+                                                        self.device)
+            bands, n_valid = _rows_quantiles(self.lib, power.data_ptr(), F, S, 1, S, S, q, self.device)
+            bands, n_valid = bands.cpu().numpy(), n_valid.cpu().numpy()
+            freq, data_power = freq.cpu().numpy(), data_power[:, 0].cpu().numpy()
+        out = periodogram.PeriodogramBands(freq=freq, q=q, bands=np.ascontiguousarray(bands.T), n_valid=n_valid,
+                                           data_power=data_power)
+        if return_samples:
+            out.X, out.idx, out.status, out.rv, out.power = X, idx, status, rv, power
         return out
 
 
