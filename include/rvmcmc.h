@@ -513,7 +513,9 @@ int rvm_logl_derivs(const rvm_plan* plan, int32_t n_chains, const double* params
  *   The order of the sum is fixed:
  *     1. per walker, t ascending in one thread, acc = fma(y[t], y[t + k], acc) from acc = 0;
  *     2. the walkers of a block of 256 (walker block b: w in [256 b, 256 b + 256), absent walkers add
- *        +0) by a binary tree over the 256 slots, slot i += slot i + h for h = 128, 64, ..., 1;
+ *        +0) by a binary tree over the 256 slots, slot i += slot i + h for h = 128, 64, ..., 1
+ *        (csrc/rvm_block_sum.h block_tree_sum: the one statement of it, for rvm_chain_cov and
+ *        rvm_pt_ladder_update's moments as well);
  *     3. the walker blocks in index order, b = 0, 1, ..., in a second small launch, then one division
  *        by W.
  *   workspace: rvm_chain_autocov_workspace_bytes(n_params, n_cols, n_lags) bytes (8 n_params x n_lags

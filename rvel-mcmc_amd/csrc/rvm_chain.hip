@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "rvm_block_sum.h"
 #include "rvm_internal.h"
 #include "rvm_launch.h"
 
@@ -64,11 +65,11 @@ __global__ void __launch_bounds__(256) chain_moments_kernel(const double* __rest
 // in the threads past the last walker), and a product with such a y adds an exact +0 -- that covers
 // t + k running past t1 - 1, the tile's lags past lag0 + n_lags - 1 (computed, never stored past the
 // padded workspace row) and W not a multiple of 256.
-// Then the block's 256 walkers by a fixed LDS tree (stride 128, 64, ... 1), one partial per lag to
+// Then the block's 256 walkers by block_tree_sum, the 16 lags side by side, one partial per lag to
 // part[p][16 tile + i][walker block]; chain_autocov_finish_kernel adds the walker blocks in index
 // order and divides by W.
 constexpr int CH_TILE = 16;
-constexpr int CH_BLOCK = 256;
+constexpr int CH_BLOCK = BLOCK_SUM_THREADS;
 
 __global__ void __launch_bounds__(CH_BLOCK) chain_autocov_kernel(const double* __restrict__ x,
                                                                  const double* __restrict__ mean, int P, int W,
@@ -102,14 +103,7 @@ __global__ void __launch_bounds__(CH_BLOCK) chain_autocov_kernel(const double* _
     }
 #pragma unroll
     for (int i = 0; i < CH_TILE; i++) s[i][tid] = acc[i];
-    __syncthreads();
-    for (int h = CH_BLOCK / 2; h > 0; h >>= 1) {
-        if (tid < h) {
-#pragma unroll
-            for (int i = 0; i < CH_TILE; i++) s[i][tid] = s[i][tid] + s[i][tid + h];
-        }
-        __syncthreads();
-    }
+    block_tree_sum(s, tid);
     if (tid < CH_TILE) {
         const size_t lpad = (size_t)CH_TILE * gridDim.x;
         part[((size_t)p * lpad + (size_t)CH_TILE * blockIdx.x + tid) * gridDim.y + blockIdx.y] = s[tid][0];
@@ -129,11 +123,9 @@ __global__ void __launch_bounds__(256) chain_autocov_finish_kernel(const double*
     acov[(size_t)p * n_lags + j] = a / (double)W;
 }
 
-static inline int ceil_div(int a, int b) { return (int)(((long long)a + b - 1) / b); }
-
 hipError_t launch_chain_record(int P, int n, const double* src, int64_t src_ld, int64_t c0, int64_t cs, double* dst,
                                int64_t dst_ld, int64_t d0, const double* lsrc, double* ldst, hipStream_t st) {
-    const dim3 grid((unsigned)ceil_div(n, 256), (unsigned)(P + (lsrc ? 1 : 0)));
+    const dim3 grid(blocks_of(n, 256), (unsigned)(P + (lsrc ? 1 : 0)));
     chain_record_kernel<<<grid, 256, 0, st>>>(P, n, src, (size_t)src_ld, (size_t)c0, (size_t)cs, dst, (size_t)dst_ld,
                                               (size_t)d0, lsrc, ldst);
     return hipGetLastError();
@@ -142,25 +134,23 @@ hipError_t launch_chain_record(int P, int n, const double* src, int64_t src_ld, 
 hipError_t launch_chain_moments(const double* x, int P, int W, int64_t t0, int64_t t1, double* mean, double* m2,
                                 hipStream_t st) {
     const size_t PW = (size_t)P * W;
-    chain_moments_kernel<<<dim3((unsigned)((PW + 255) / 256)), 256, 0, st>>>(x, PW, t0, t1, mean, m2);
+    chain_moments_kernel<<<dim3(blocks_of(PW, 256)), 256, 0, st>>>(x, PW, t0, t1, mean, m2);
     return hipGetLastError();
 }
 
 // workspace doubles: [P][16 tiles][walker blocks]
 size_t chain_autocov_workspace_doubles(int P, int W, int n_lags) {
-    return (size_t)P * CH_TILE * (size_t)ceil_div(n_lags, CH_TILE) * (size_t)ceil_div(W, CH_BLOCK);
+    return (size_t)P * CH_TILE * (size_t)blocks_of(n_lags, CH_TILE) * (size_t)blocks_of(W, CH_BLOCK);
 }
 
 hipError_t launch_chain_autocov(const double* x, const double* mean, int P, int W, int64_t t0, int64_t t1, int lag0,
                                 int n_lags, double* acov, double* part, hipStream_t st) {
-    const int tiles = ceil_div(n_lags, CH_TILE), nwb = ceil_div(W, CH_BLOCK);
-    chain_autocov_kernel<<<dim3((unsigned)tiles, (unsigned)nwb, (unsigned)P), CH_BLOCK, 0, st>>>(x, mean, P, W, t0, t1,
-                                                                                               lag0, part);
+    const unsigned tiles = blocks_of(n_lags, CH_TILE), nwb = blocks_of(W, CH_BLOCK);
+    chain_autocov_kernel<<<dim3(tiles, nwb, (unsigned)P), CH_BLOCK, 0, st>>>(x, mean, P, W, t0, t1, lag0, part);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    chain_autocov_finish_kernel<<<dim3((unsigned)ceil_div(P * n_lags, 256)), 256, 0, st>>>(part, P, n_lags,
-                                                                                           CH_TILE * tiles, nwb, W,
-                                                                                           acov);
+    chain_autocov_finish_kernel<<<dim3(blocks_of(P * n_lags, 256)), 256, 0, st>>>(
+        part, P, n_lags, (int)(CH_TILE * tiles), (int)nwb, W, acov);
     return hipGetLastError();
 }
 

@@ -73,6 +73,23 @@ __global__ void __launch_bounds__(GB_BLOCK)
     }
 }
 
+// One pass of a thread over the epochs 0 .. N - 1, as prepare and centre make it twice each (the mean, then the
+// sums): the loads of GL_BATCH epochs are issued together -- load(i) returns what the thread needs of epoch i; a
+// batch that runs past the end loads epoch N - 1 again and does not use it -- and then used in order, use(i, e) for
+// i ascending.  A thread's chain of fmas is serial; its loads need not be.  The order of the use calls is the
+// definition's order of operations.
+template <typename Load, typename Use>
+__device__ __forceinline__ void gls_epochs(int N, const Load& load, const Use& use) {
+    for (int i0 = 0; i0 < N; i0 += GL_BATCH) {
+        decltype(load(0)) e[GL_BATCH];
+#pragma unroll
+        for (int j = 0; j < GL_BATCH; j++) e[j] = load(i0 + j < N ? i0 + j : N - 1);
+#pragma unroll
+        for (int j = 0; j < GL_BATCH; j++)
+            if (i0 + j < N) use(i0 + j, e[j]);
+    }
+}
+
 // Step 2 of the definition.  Row k of u holds c on entry and u on exit, of v likewise s and v.
 __global__ void __launch_bounds__(GP_BLOCK)
     gls_prepare_kernel(const double* __restrict__ w, int N, int64_t ld, int F, int float_mean, double* __restrict__ u,
@@ -83,44 +100,26 @@ __global__ void __launch_bounds__(GP_BLOCK)
     if (k >= F) return;
     double* cu = u + (size_t)k * (size_t)ld;
     double* sv = v + (size_t)k * (size_t)ld;
-    // (GL_BATCH epochs' loads are issued together, then summed in order: a thread's chain is serial, its loads
-    // need not be)
+    struct Epoch {
+        double c, s, w;
+    };
+    const auto load = [&](int i) { return Epoch{cu[i], sv[i], w[i]}; };
     double C = 0.0, S = 0.0;
     if (float_mean)
-        for (int i0 = 0; i0 < N; i0 += GL_BATCH) {
-            double cb[GL_BATCH], sb[GL_BATCH], wb[GL_BATCH];
-#pragma unroll
-            for (int j = 0; j < GL_BATCH; j++) {
-                const int i = i0 + j < N ? i0 + j : N - 1;
-                cb[j] = cu[i], sb[j] = sv[i], wb[j] = w[i];
-            }
-#pragma unroll
-            for (int j = 0; j < GL_BATCH; j++)
-                if (i0 + j < N) {
-                    C = fma(wb[j], cb[j], C);
-                    S = fma(wb[j], sb[j], S);
-                }
-        }
+        gls_epochs(N, load, [&](int, const Epoch& e) {
+            C = fma(e.w, e.c, C);
+            S = fma(e.w, e.s, S);
+        });
     double CC = 0.0, SS = 0.0, CS = 0.0;
-    for (int i0 = 0; i0 < N; i0 += GL_BATCH) {
-        double cb[GL_BATCH], sb[GL_BATCH], wb[GL_BATCH];
-#pragma unroll
-        for (int j = 0; j < GL_BATCH; j++) {
-            const int i = i0 + j < N ? i0 + j : N - 1;
-            cb[j] = cu[i], sb[j] = sv[i], wb[j] = w[i];
-        }
-#pragma unroll
-        for (int j = 0; j < GL_BATCH; j++)
-            if (i0 + j < N) {
-                const double ct = cb[j] - C, st = sb[j] - S;
-                const double ui = wb[j] * ct, vi = wb[j] * st;
-                CC = fma(ui, ct, CC);
-                SS = fma(vi, st, SS);
-                CS = fma(ui, st, CS);
-                cu[i0 + j] = ui;
-                sv[i0 + j] = vi;
-            }
-    }
+    gls_epochs(N, load, [&](int i, const Epoch& e) {
+        const double ct = e.c - C, st = e.s - S;
+        const double ui = e.w * ct, vi = e.w * st;
+        CC = fma(ui, ct, CC);
+        SS = fma(vi, st, SS);
+        CS = fma(ui, st, CS);
+        cu[i] = ui;
+        sv[i] = vi;
+    });
     cc_out[k] = CC;
     ss_out[k] = SS;
     cs_out[k] = CS;
@@ -135,38 +134,21 @@ __global__ void __launch_bounds__(GC_BLOCK)
     const int64_t s = (int64_t)blockIdx.x * GC_BLOCK + threadIdx.x;
     if (s >= S) return;
     const double* col = model ? model + (size_t)s : nullptr;
+    struct Epoch {
+        double y, w;
+    };
+    const auto load = [&](int i) {
+        return Epoch{col ? data[i] - col[(size_t)i * (size_t)model_ld] : data[i], w[i]};
+    };
     double m = 0.0;
-    if (float_mean)
-        for (int i0 = 0; i0 < N; i0 += GL_BATCH) {
-            double yb[GL_BATCH], wb[GL_BATCH];
-#pragma unroll
-            for (int j = 0; j < GL_BATCH; j++) {
-                const int i = i0 + j < N ? i0 + j : N - 1;
-                yb[j] = col ? data[i] - col[(size_t)i * (size_t)model_ld] : data[i];
-                wb[j] = w[i];
-            }
-#pragma unroll
-            for (int j = 0; j < GL_BATCH; j++)
-                if (i0 + j < N) m = fma(wb[j], yb[j], m);
-        }
+    if (float_mean) gls_epochs(N, load, [&](int, const Epoch& e) { m = fma(e.w, e.y, m); });
     double yy = 0.0;
-    for (int i0 = 0; i0 < N; i0 += GL_BATCH) {
-        double yb[GL_BATCH], wb[GL_BATCH];
-#pragma unroll
-        for (int j = 0; j < GL_BATCH; j++) {
-            const int i = i0 + j < N ? i0 + j : N - 1;
-            yb[j] = col ? data[i] - col[(size_t)i * (size_t)model_ld] : data[i];
-            wb[j] = w[i];
-        }
-#pragma unroll
-        for (int j = 0; j < GL_BATCH; j++)
-            if (i0 + j < N) {
-                const double zi = yb[j] - m;
-                const double wz = wb[j] * zi;
-                z[(size_t)(i0 + j) * (size_t)zld + (size_t)s] = zi;
-                yy = fma(wz, zi, yy);
-            }
-    }
+    gls_epochs(N, load, [&](int i, const Epoch& e) {
+        const double zi = e.y - m;
+        const double wz = e.w * zi;
+        z[(size_t)i * (size_t)zld + (size_t)s] = zi;
+        yy = fma(wz, zi, yy);
+    });
     yy_out[s] = yy;
 }
 
@@ -275,8 +257,6 @@ __global__ void __launch_bounds__(GT_BLOCK)
         }
     }
 }
-
-static inline unsigned blocks_of(uint64_t n, int per) { return (unsigned)((n + (uint64_t)per - 1) / (uint64_t)per); }
 
 // frequencies of a chunk of rvm_gls_power: a multiple of the product kernel's tile
 int64_t gls_chunk_freqs(int N) {

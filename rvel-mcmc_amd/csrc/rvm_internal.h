@@ -89,6 +89,12 @@ constexpr int RVM_HW_MARK = RVM_HW_STATS + 3 + 3;
 constexpr int RVM_HW_WAIT = RVM_HW_MARK + 2 * RVM_HEDGE_GROUPS_MAX;
 constexpr int RVM_HW_WORDS = RVM_HW_WAIT + 3;
 
+// Blocks of `per` items that cover n items: the block count of every sampler and read-out launcher, in 64-bit
+// arithmetic (n + per - 1 does not wrap for any count the ABI admits, INT32_MAX included)
+inline unsigned blocks_of(uint64_t n, int per) { return (unsigned)((n + (uint64_t)per - 1) / (uint64_t)per); }
+// The quiet NaN the read-outs write where there is no value: sign 0, payload 0
+constexpr double RVM_QNAN = __builtin_bit_cast(double, (uint64_t)0x7FF8000000000000ull);
+
 // Epoch schedule of one integration direction (t >= 0 ascending from 0, or t < 0 descending).
 struct DirSched {
     int32_t n_epochs;

@@ -182,39 +182,38 @@ __global__ void fd_params_kernel(int P, int n, const double* __restrict__ x, dou
         for (int s = 0; s < S; s++) out[(size_t)p * WW + (size_t)s * n + c] = fd_point(x, fl, rel, n, p, s * n + c);
 }
 
-static inline dim3 grid1(int n) { return dim3((n + 255) / 256); }
-
 hipError_t launch_stretch_propose(int P, int n0, int64_t s0b, const double* x, int n1, const double* c, double a,
                                   uint64_t seed, uint64_t it, uint32_t half, const double* draws, double* q,
                                   double* z, hipStream_t st) {
-    stretch_propose_kernel<<<grid1(n0), 256, 0, st>>>(P, n0, s0b, x, n1, c, a, seed, it, half, draws, q, z);
+    stretch_propose_kernel<<<blocks_of(n0, 256), 256, 0, st>>>(P, n0, s0b, x, n1, c, a, seed, it, half, draws, q, z);
     return hipGetLastError();
 }
 hipError_t launch_stretch_accept(int P, int n0, int64_t s0b, double* x, double* lnp, const double* q,
                                  const double* lnp_new, const double* z, uint64_t seed, uint64_t it, uint32_t half,
                                  const double* draws, int32_t* acc, hipStream_t st) {
-    stretch_accept_kernel<<<grid1(n0), 256, 0, st>>>(P, n0, s0b, x, lnp, q, lnp_new, z, seed, it, half, draws, acc);
+    stretch_accept_kernel<<<blocks_of(n0, 256), 256, 0, st>>>(P, n0, s0b, x, lnp, q, lnp_new, z, seed, it, half, draws,
+                                                              acc);
     return hipGetLastError();
 }
 hipError_t launch_stretch_iteration_end(const IterEndArgs& g, hipStream_t st) {
     if (g.dim <= 16)
-        stretch_iteration_end_kernel<16><<<grid1(2 * g.n), 256, 0, st>>>(g);
+        stretch_iteration_end_kernel<16><<<blocks_of(2 * (uint64_t)g.n, 256), 256, 0, st>>>(g);
     else
-        stretch_iteration_end_kernel<0><<<grid1(2 * g.n), 256, 0, st>>>(g);
+        stretch_iteration_end_kernel<0><<<blocks_of(2 * (uint64_t)g.n, 256), 256, 0, st>>>(g);
     return hipGetLastError();
 }
 hipError_t launch_mh_propose(int P, int n, int64_t b, const double* x, const double* scales, double step,
                              uint64_t seed, uint64_t it, const double* draws, double* q, hipStream_t st) {
-    mh_propose_kernel<<<grid1(n), 256, 0, st>>>(P, n, b, x, scales, step, seed, it, draws, q);
+    mh_propose_kernel<<<blocks_of(n, 256), 256, 0, st>>>(P, n, b, x, scales, step, seed, it, draws, q);
     return hipGetLastError();
 }
 hipError_t launch_mh_accept(int P, int n, int64_t b, double* x, double* lnp, const double* q, const double* lnp_new,
                             uint64_t seed, uint64_t it, const double* draws, int32_t* acc, hipStream_t st) {
-    mh_accept_kernel<<<grid1(n), 256, 0, st>>>(P, n, b, x, lnp, q, lnp_new, seed, it, draws, acc);
+    mh_accept_kernel<<<blocks_of(n, 256), 256, 0, st>>>(P, n, b, x, lnp, q, lnp_new, seed, it, draws, acc);
     return hipGetLastError();
 }
 hipError_t launch_fd_params(int P, int n, const double* x, double rel, const double* fl, double* out, hipStream_t st) {
-    fd_params_kernel<<<grid1(n), 256, 0, st>>>(P, n, x, rel, fl, out);
+    fd_params_kernel<<<blocks_of(n, 256), 256, 0, st>>>(P, n, x, rel, fl, out);
     return hipGetLastError();
 }
 

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "rvm_block_sum.h"
 #include "rvm_device.h"
 #include "rvm_internal.h"
 #include "rvm_launch.h"
@@ -97,7 +98,7 @@ __global__ void __launch_bounds__(SEL_BLOCK)
             if (kp == gp[g]) atomicAdd(&h[g * SEL_BINS + d], 1u);
     };
     const double* xr = x + row * row_stride;
-    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const double nan = RVM_QNAN;
     for (uint64_t u = u0; u < u1; u++) {
         const uint64_t o = u / segs, s = u - o * segs;
         const double* line = xr + o * outer_stride;
@@ -169,7 +170,7 @@ __global__ void __launch_bounds__(SEL_BLOCK)
             if (m == 0) st->n_groups = 0;
         }
         if (m == 0) {
-            if (tid < Q.n_q) out[row * Q.n_q + tid] = __longlong_as_double(0x7FF8000000000000ll);
+            if (tid < Q.n_q) out[row * Q.n_q + tid] = RVM_QNAN;
             return;
         }
     }
@@ -279,11 +280,11 @@ hipError_t launch_rows_quantiles(const double* x, int n_rows, int64_t row_stride
 // and one-wave blocks because the walkers and the pairs are all the parallelism there is: a walker's
 // steps are one thread's, in order.
 // chain_cov_finish_kernel: block (p, q <= p) adds the walkers in rvm_chain_autocov's order -- each block of
-// 256 walkers by the LDS tree (stride 128, 64, ... 1; an absent walker is +0), the walker blocks in index
-// order -- divides once and writes cov[p][q] and cov[q][p].
+// 256 walkers by block_tree_sum (an absent walker is +0), the walker blocks in index order -- divides once and
+// writes cov[p][q] and cov[q][p].
 constexpr int CV_TILE = 2;
 constexpr int CV_WAVE = 64;
-constexpr int CV_BLOCK = 256;
+constexpr int CV_BLOCK = BLOCK_SUM_THREADS;
 
 __global__ void __launch_bounds__(CV_WAVE) chain_cov_kernel(const double* __restrict__ x,
                                                             const double* __restrict__ center, int P, int W,
@@ -335,38 +336,32 @@ __global__ void __launch_bounds__(CV_WAVE) chain_cov_kernel(const double* __rest
 
 __global__ void __launch_bounds__(CV_BLOCK) chain_cov_finish_kernel(const double* __restrict__ sums, int P, int W,
                                                                     long long nW, double* __restrict__ cov) {
-    __shared__ double s[CV_BLOCK];
+    __shared__ double s[1][CV_BLOCK];
     const int p = (int)(blockIdx.x / (unsigned)P), q = (int)(blockIdx.x - (unsigned)p * (unsigned)P);
     if (q > p) return;
     const int tid = (int)threadIdx.x;
     const double* r = sums + ((size_t)p * P + q) * W;
     double total = 0.0;
     for (int w0 = 0; w0 < W; w0 += CV_BLOCK) {
-        s[tid] = w0 + tid < W ? r[w0 + tid] : 0.0;
-        __syncthreads();
-        for (int h = CV_BLOCK / 2; h > 0; h >>= 1) {
-            if (tid < h) s[tid] = s[tid] + s[tid + h];
-            __syncthreads();
-        }
-        if (tid == 0) total = w0 == 0 ? s[0] : total + s[0];
+        s[0][tid] = w0 + tid < W ? r[w0 + tid] : 0.0;
+        block_tree_sum(s, tid);
+        if (tid == 0) total = w0 == 0 ? s[0][0] : total + s[0][0];
         __syncthreads();
     }
     if (tid == 0) {
-        const double v = nW > 1 ? total / (double)(nW - 1) : __longlong_as_double(0x7FF8000000000000ll);
+        const double v = nW > 1 ? total / (double)(nW - 1) : RVM_QNAN;
         cov[(size_t)p * P + q] = v;
         cov[(size_t)q * P + p] = v;
     }
 }
-
-static inline int ceil_div(int a, int b) { return (int)(((long long)a + b - 1) / b); }
 
 // workspace doubles: [P][P][W], a walker's sums (the entries p >= q are used)
 size_t chain_cov_workspace_doubles(int P, int W) { return (size_t)P * P * (size_t)W; }
 
 hipError_t launch_chain_cov(const double* x, int P, int W, int64_t t0, int64_t t1, const double* center, double* cov,
                             double* sums, hipStream_t st) {
-    const int nt = ceil_div(P, CV_TILE);
-    chain_cov_kernel<<<dim3((unsigned)nt, (unsigned)nt, (unsigned)ceil_div(W, CV_WAVE)), CV_WAVE, 0, st>>>(
+    const unsigned nt = blocks_of(P, CV_TILE);
+    chain_cov_kernel<<<dim3(nt, nt, blocks_of(W, CV_WAVE)), CV_WAVE, 0, st>>>(
         x, center, P, W, t0, t1, sums);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -405,8 +400,7 @@ __global__ void __launch_bounds__(256) chain_draw_kernel(const double* __restric
 
 hipError_t launch_chain_draw(const double* x, int P, int W, int64_t t0, int64_t t1, int S, uint64_t seed,
                              uint64_t draw_id, const double* draws, double* xo, int64_t* idx, hipStream_t st) {
-    chain_draw_kernel<<<dim3((unsigned)ceil_div(S, 256)), 256, 0, st>>>(x, P, W, t0, t1, S, seed, draw_id, draws, xo,
-                                                                        idx);
+    chain_draw_kernel<<<dim3(blocks_of(S, 256)), 256, 0, st>>>(x, P, W, t0, t1, S, seed, draw_id, draws, xo, idx);
     return hipGetLastError();
 }
 

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "rvm_block_sum.h"
 #include "rvm_device.h"
 #include "rvm_internal.h"
 #include "rvm_launch.h"
@@ -110,24 +111,20 @@ __global__ void pt_swap_kernel(int P, int T, int Wh, const double* __restrict__ 
 // swapped[p][0..W) (integer sums do not depend on the order).  Rows T-1 .. 2T-2 (launched only when
 // the moments are asked for): sum lnp and sum lnp^2 over temperature t's W walkers in the index
 // order j = 0 .. W-1 (half 0's columns t Wh .. t Wh + Wh - 1, then half 1's): thread i adds j = i,
-// i + 256, ... in that order, then an LDS tree over the 256 slots -- a fixed order, no atomics, the
-// same bits from run to run.
-__global__ void __launch_bounds__(256) pt_ladder_stats_kernel(PtLadderArgs g) {
-    __shared__ int64_t sn[256];
-    __shared__ double s1[256], s2[256];
+// i + 256, ... in that order, then block_tree_sum over the 256 slots, the two sums side by side -- a
+// fixed order, no atomics, the same bits from run to run.
+__global__ void __launch_bounds__(BLOCK_SUM_THREADS) pt_ladder_stats_kernel(PtLadderArgs g) {
+    __shared__ int64_t sn[1][BLOCK_SUM_THREADS];
+    __shared__ double sm[2][BLOCK_SUM_THREADS];  // sum lnp, sum lnp^2
     const int tid = (int)threadIdx.x, row = (int)blockIdx.x;  // (the branches below are block-uniform)
     const int Wh = g.Wh, W = 2 * g.Wh;
     if (row < g.T - 1) {
         const int32_t* r = g.swapped + (size_t)row * W;
         int64_t part = 0;
-        for (int w = tid; w < W; w += 256) part += r[w];
-        sn[tid] = part;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (tid < s) sn[tid] += sn[tid + s];
-            __syncthreads();
-        }
-        if (tid == 0) g.ws_totals[row] = sn[0];
+        for (int w = tid; w < W; w += BLOCK_SUM_THREADS) part += r[w];
+        sn[0][tid] = part;
+        block_tree_sum(sn, tid);
+        if (tid == 0) g.ws_totals[row] = sn[0][0];
         return;
     }
     const int t = row - (g.T - 1);
@@ -135,24 +132,17 @@ __global__ void __launch_bounds__(256) pt_ladder_stats_kernel(PtLadderArgs g) {
     const double* l0 = g.lnp0 + (size_t)t * Wh;
     const double* l1 = g.lnp1 + (size_t)t * Wh;
     double a = 0.0, b = 0.0;
-    for (int j = tid; j < W; j += 256) {
+    for (int j = tid; j < W; j += BLOCK_SUM_THREADS) {
         const double v = j < Wh ? l0[j] : l1[j - Wh];
         a = a + v;
         b = b + v * v;
     }
-    s1[tid] = a;
-    s2[tid] = b;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) {
-            s1[tid] = s1[tid] + s1[tid + s];
-            s2[tid] = s2[tid] + s2[tid + s];
-        }
-        __syncthreads();
-    }
+    sm[0][tid] = a;
+    sm[1][tid] = b;
+    block_tree_sum(sm, tid);
     if (tid == 0) {
-        g.ws_moments[2 * t] = s1[0];
-        g.ws_moments[2 * t + 1] = s2[0];
+        g.ws_moments[2 * t] = sm[0][0];
+        g.ws_moments[2 * t + 1] = sm[1][0];
     }
 }
 
@@ -211,30 +201,29 @@ __global__ void pt_ladder_adapt_kernel(PtLadderArgs g) {
     pt_ladder_pass(g, true, ok, driven);
 }
 
-static inline dim3 grid1(int n) { return dim3((unsigned)(((int64_t)n + 255) / 256)); }
-
 hipError_t launch_pt_stretch_propose(int P, int T, int Wh, const double* x, const double* c, double a, uint64_t seed,
                                      uint64_t it, uint32_t half, const double* draws, double* q, double* z,
                                      hipStream_t st) {
-    pt_stretch_propose_kernel<<<grid1(T * Wh), 256, 0, st>>>(P, T, Wh, x, c, a, seed, it, half, draws, q, z);
+    pt_stretch_propose_kernel<<<blocks_of(T * Wh, 256), 256, 0, st>>>(P, T, Wh, x, c, a, seed, it, half, draws, q, z);
     return hipGetLastError();
 }
 hipError_t launch_pt_stretch_accept(int P, int T, int Wh, const double* betas, double* x, double* lnp,
                                     const double* q, const double* lnp_new, const double* z, uint64_t seed,
                                     uint64_t it, uint32_t half, const double* draws, int32_t* acc, hipStream_t st) {
-    pt_stretch_accept_kernel<<<grid1(T * Wh), 256, 0, st>>>(P, T, Wh, betas, x, lnp, q, lnp_new, z, seed, it, half,
-                                                            draws, acc);
+    pt_stretch_accept_kernel<<<blocks_of(T * Wh, 256), 256, 0, st>>>(P, T, Wh, betas, x, lnp, q, lnp_new, z, seed, it,
+                                                                     half, draws, acc);
     return hipGetLastError();
 }
 hipError_t launch_pt_swap(int P, int T, int Wh, const double* betas, double* x0, double* x1, double* lnp0,
                           double* lnp1, uint64_t seed, uint64_t it, const double* draws, int32_t* swapped,
                           hipStream_t st) {
-    pt_swap_kernel<<<grid1(2 * Wh), 256, 0, st>>>(P, T, Wh, betas, x0, x1, lnp0, lnp1, seed, it, draws, swapped);
+    pt_swap_kernel<<<blocks_of(2 * Wh, 256), 256, 0, st>>>(P, T, Wh, betas, x0, x1, lnp0, lnp1, seed, it, draws,
+                                                           swapped);
     return hipGetLastError();
 }
 hipError_t launch_pt_ladder_update(const PtLadderArgs& g, hipStream_t st) {
     const unsigned rows = (unsigned)(g.T - 1) + (g.moments ? (unsigned)g.T : 0u);
-    pt_ladder_stats_kernel<<<dim3(rows), 256, 0, st>>>(g);
+    pt_ladder_stats_kernel<<<dim3(rows), BLOCK_SUM_THREADS, 0, st>>>(g);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     pt_ladder_adapt_kernel<<<dim3(1), 64, 0, st>>>(g);

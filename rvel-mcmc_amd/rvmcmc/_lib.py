@@ -201,6 +201,12 @@ def ptr(t) -> int:
     return t.data_ptr() if t is not None else 0
 
 
+def workspace(nbytes, dtype, device, floor=1):
+    """An uninitialised device workspace of nbytes (what a *_workspace_bytes entry point answered) as 8-byte
+    elements of dtype, and at least `floor` of them: no entry point takes a null workspace."""
+    return _torch().empty(max(nbytes // 8, floor), dtype=dtype, device=device)
+
+
 def stream_handle(stream=None) -> int:
     """hipStream_t of a torch stream (default: the current stream of the current device)."""
     import torch

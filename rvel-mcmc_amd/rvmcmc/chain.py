@@ -158,8 +158,7 @@ def _rows_quantiles(lib, ptr, n_rows, row_stride, n_outer, outer_stride, n_inner
     torch = _torch()
     out = torch.empty((n_rows, len(q)), dtype=torch.float64, device=device)
     n_valid = torch.empty(n_rows, dtype=torch.int64, device=device)
-    ws = torch.empty(max(lib.rvm_rows_quantiles_workspace_bytes(n_rows, len(q)) // 8, 1), dtype=torch.int64,
-                     device=device)
+    ws = _lib.workspace(lib.rvm_rows_quantiles_workspace_bytes(n_rows, len(q)), torch.int64, device)
     qc = (C.c_double * len(q))(*q)
     _lib.check(lib.rvm_rows_quantiles(ptr, n_rows, row_stride, n_outer, outer_stride, n_inner, qc, len(q),
                                       out.data_ptr(), n_valid.data_ptr(), ws.data_ptr(), _lib.stream_handle()),
@@ -274,7 +273,7 @@ class ChainRecorder:
         if n_lags not in self._work:
             nbytes = self.lib.rvm_chain_autocov_workspace_bytes(self.n_params, self.n_walkers, n_lags)
             self._work[n_lags] = (torch.empty((self.n_params, n_lags), dtype=torch.float64, device=self.device),
-                                  torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=self.device))
+                                  _lib.workspace(nbytes, torch.float64, self.device))
         acov, ws = self._work[n_lags]
         _lib.check(self.lib.rvm_chain_autocov(self._chain.data_ptr(), mean.data_ptr(), self.n_params, self.n_walkers,
                                               t0, t1, lag0, n_lags, acov.data_ptr(), ws.data_ptr(),
@@ -285,9 +284,7 @@ class ChainRecorder:
         """ChainDiagnostics of the recorded steps [discard, n).  Synchronises: one small [P][n_lags]
         copy per lag block of the window search, and the [P] results."""
         torch = _torch()
-        t0, t1 = int(discard), self.n
-        if t0 < 0 or t0 >= t1:
-            raise ValueError(f"discard must leave at least one of the {self.n} recorded steps")
+        t0, t1 = self._range(discard)
         n, W, P = t1 - t0, self.n_walkers, self.n_params
         with torch.cuda.device(self.device):
             mean, m2 = self._moments(t0, t1, 0)
@@ -346,8 +343,7 @@ class ChainRecorder:
             quant, _ = _rows_quantiles(self.lib, self._chain.data_ptr() + 8 * t0 * P * W, P, W, n, P * W, W, q,
                                        self.device)
             cov = torch.empty((P, P), dtype=torch.float64, device=self.device)
-            ws = torch.empty(max(self.lib.rvm_chain_cov_workspace_bytes(P, W) // 8, 1), dtype=torch.float64,
-                             device=self.device)
+            ws = _lib.workspace(self.lib.rvm_chain_cov_workspace_bytes(P, W), torch.float64, self.device)
             _lib.check(self.lib.rvm_chain_cov(self._chain.data_ptr(), P, W, t0, t1, center.data_ptr(), cov.data_ptr(),
                                               ws.data_ptr(), _lib.stream_handle()), "rvm_chain_cov")
             center, quant, cov = center.cpu().numpy(), quant.cpu().numpy(), cov.cpu().numpy()
@@ -377,13 +373,37 @@ class ChainRecorder:
                                                _lib.stream_handle()), "rvm_chain_draw")
         return X, idx
 
-    def _samples(self, X):
-        """The caller's samples [P][S] as predict() and residual_periodogram() take them, contiguous."""
+    def _evaluator(self, with_obs, lacks):
+        """(state, obs) of the sampler, what predict() and residual_periodogram() evaluate the RV with: TypeError
+        `has no <lacks>` without a state and a parameter map (with_obs: and an observation set, else obs is None)."""
+        sampler = self.sampler
+        state, obs = getattr(sampler, "state", None), getattr(sampler, "obs", None) if with_obs else None
+        if state is None or (with_obs and obs is None) or not hasattr(sampler, "pmap"):
+            raise TypeError(f"{type(sampler).__name__} has no {lacks}")
+        return state, obs
+
+    def _model_rv(self, state, obs, n_samples, discard, seed, samples):
+        """(masked, kept): n_samples states drawn from the steps [discard, n), or the caller's samples [P][S]; one
+        likelihood launch with rv_out on obs (the sampler's parameter map and Hill factor).  masked: rv
+        [n_epochs][S], NaN in the columns that are not RVM_STATUS_OK; kept: the return_samples fields."""
         torch = _torch()
+        X, idx = (samples, None) if samples is not None else self.draw(n_samples, discard, seed)
         if (not torch.is_tensor(X) or X.dtype != torch.float64 or X.dim() != 2 or X.shape[0] != self.n_params
                 or X.shape[1] < 1 or X.device != self._chain.device):
             raise ValueError("samples must be a float64 tensor [n_params][S] on the recorder's device")
-        return X.contiguous()
+        X = X.contiguous()
+        hf = getattr(self.sampler, "hill_factor", state.hillRadiusFactor)
+        with torch.cuda.device(self.device):
+            _, status, rv = state.get_logp_batch(obs, X, hill_factor=hf, want_rv=True, pmap=self.sampler.pmap)
+            masked = torch.where((status == _lib.RVM_STATUS_OK)[None, :], rv, torch.full_like(rv, float("nan")))
+        return masked, dict(X=X, idx=idx, status=status, rv=rv)
+
+    def _bands(self, rows, q):
+        """(bands [n_q][n_rows], n_valid [n_rows]) on the host: rvm_rows_quantiles of a device matrix [n_rows][S]."""
+        n_rows, S = (int(v) for v in rows.shape)
+        with _torch().cuda.device(self.device):
+            bands, n_valid = _rows_quantiles(self.lib, rows.data_ptr(), n_rows, S, 1, S, S, q, self.device)
+            return np.ascontiguousarray(bands.cpu().numpy().T), n_valid.cpu().numpy()
 
     def predict(self, times, n_samples=1024, discard=0, q=DEFAULT_Q, seed=0, samples=None, return_samples=False):
         """RvBands: the quantiles q of the model RV at `times` over n_samples states drawn from the recorded
@@ -395,7 +415,6 @@ class ChainRecorder:
         epochs' rows; n_valid counts the samples behind each epoch.  At most RVM_MAX_EPOCHS_PER_DIRECTION
         epochs with t >= 0 and as many with t < 0 (ValueError beyond).  Synchronises for the [n_q][n_times]
         result."""
-        torch = _torch()
         times = np.ascontiguousarray(np.asarray(times, dtype=np.float64).ravel())
         if len(times) < 1 or not np.all(np.isfinite(times)):
             raise ValueError("times must be a non-empty array of finite epochs")
@@ -404,29 +423,14 @@ class ChainRecorder:
             raise ValueError(f"at most {cap} epochs with t >= 0 and {cap} with t < 0 per call "
                              f"(RVM_MAX_EPOCHS_PER_DIRECTION)")
         q = _q_array(q)
-        sampler = self.sampler
-        state = getattr(sampler, "state", None)
-        if state is None or not hasattr(sampler, "pmap"):
-            raise TypeError(f"{type(sampler).__name__} has no state / pmap: nothing to evaluate the RV with")
-        idx = None
-        if samples is None:
-            X, idx = self.draw(n_samples, discard, seed)
-        else:
-            X = self._samples(samples)
+        state, _ = self._evaluator(False, "state / pmap: nothing to evaluate the RV with")
         key = times.tobytes()
         if self._epochs is None or self._epochs[0] != key:
             self._epochs = (key, Epochs(times))  # (keeps the plan plan_for caches on it)
-        hf = getattr(sampler, "hill_factor", state.hillRadiusFactor)
-        with torch.cuda.device(self.device):
-            _, status, rv = state.get_logp_batch(self._epochs[1], X, hill_factor=hf, want_rv=True, pmap=sampler.pmap)
-            masked = torch.where((status == _lib.RVM_STATUS_OK)[None, :], rv, torch.full_like(rv, float("nan")))
-            S = int(X.shape[1])
-            bands, n_valid = _rows_quantiles(self.lib, masked.data_ptr(), len(times), S, 1, S, S, q, self.device)
-            bands, n_valid = bands.cpu().numpy(), n_valid.cpu().numpy()
-        out = RvBands(times=times, q=q, bands=np.ascontiguousarray(bands.T), n_valid=n_valid)
-        if return_samples:
-            out.X, out.idx, out.status, out.rv = X, idx, status, rv
-        return out
+        masked, kept = self._model_rv(state, self._epochs[1], n_samples, discard, seed, samples)
+        bands, n_valid = self._bands(masked, q)
+        out = RvBands(times=times, q=q, bands=bands, n_valid=n_valid)
+        return dataclasses.replace(out, **kept) if return_samples else out
 
     def residual_periodogram(self, grid=None, n_samples=1024, discard=0, q=DEFAULT_Q, seed=0, samples=None,
                              float_mean=True, return_samples=False):
@@ -440,39 +444,21 @@ class ChainRecorder:
         for the [n_q][F], [F] and [F] results."""
         from . import engine, periodogram
 
-        torch = _torch()
-        sampler = self.sampler
-        state, obs = getattr(sampler, "state", None), getattr(sampler, "obs", None)
-        if state is None or obs is None or not hasattr(sampler, "pmap"):
-            raise TypeError(f"{type(sampler).__name__} has no obs / state / pmap: nothing to take residuals from")
+        state, obs = self._evaluator(True, "obs / state / pmap: nothing to take residuals from")
         t, rvobs, er = engine.obs_arrays(obs)
         tau, w = periodogram.series_inputs(t, er, float_mean)
-        grid = periodogram._grid(grid, t)
-        q = _q_array(q)
-        idx = None
-        if samples is None:
-            X, idx = self.draw(n_samples, discard, seed)
-        else:
-            X = self._samples(samples)
-        hf = getattr(sampler, "hill_factor", state.hillRadiusFactor)
-        F = grid[2]
-        with torch.cuda.device(self.device):
-            _, status, rv = state.get_logp_batch(obs, X, hill_factor=hf, want_rv=True, pmap=sampler.pmap)
-            masked = torch.where((status == _lib.RVM_STATUS_OK)[None, :], rv, torch.full_like(rv, float("nan")))
-            S = int(X.shape[1])
-            dev = [torch.as_tensor(np.ascontiguousarray(a), device=self.device) for a in (tau, w, rvobs)]
-            power, freq = periodogram.power_on_device(self.lib, dev[0], dev[1], dev[2], masked.contiguous(), S, grid,
-                                                      float_mean, self.device)
-            data_power, _ = periodogram.power_on_device(self.lib, dev[0], dev[1], dev[2], None, 1, grid, float_mean,
-                                                        self.device)
-            bands, n_valid = _rows_quantiles(self.lib, power.data_ptr(), F, S, 1, S, S, q, self.device)
-            bands, n_valid = bands.cpu().numpy(), n_valid.cpu().numpy()
+        grid, q = periodogram._grid(grid, t), _q_array(q)
+        masked, kept = self._model_rv(state, obs, n_samples, discard, seed, samples)
+        S = int(masked.shape[1])
+        with _torch().cuda.device(self.device):
+            series = periodogram.upload_series(tau, w, rvobs, self.device)
+            power, freq = periodogram.power_on_device(self.lib, series, masked.contiguous(), S, grid, float_mean,
+                                                      self.device)
+            data_power, _ = periodogram.power_on_device(self.lib, series, None, 1, grid, float_mean, self.device)
+            bands, n_valid = self._bands(power, q)
             freq, data_power = freq.cpu().numpy(), data_power[:, 0].cpu().numpy()
-        out = periodogram.PeriodogramBands(freq=freq, q=q, bands=np.ascontiguousarray(bands.T), n_valid=n_valid,
-                                           data_power=data_power)
-        if return_samples:
-            out.X, out.idx, out.status, out.rv, out.power = X, idx, status, rv, power
-        return out
+        out = periodogram.PeriodogramBands(freq=freq, q=q, bands=bands, n_valid=n_valid, data_power=data_power)
+        return dataclasses.replace(out, power=power, **kept) if return_samples else out
 
 
 def run_mcmc(sampler, n_steps, recorder=None):

@@ -111,15 +111,22 @@ def series_inputs(t, sigma, float_mean=True):
     return t - (t.min() + t.max()) / 2.0, iv / iv.sum()
 
 
-def power_on_device(lib, tau, w, data, model, n_series, grid, float_mean, device):
-    """rvm_gls_power on the current stream: (power [F][S], freq [F]) device tensors.  tau, w, data: device
-    tensors [N]; model: None or a contiguous device tensor [N][S]."""
+def upload_series(tau, w, data, device):
+    """(tau, w, data) as float64 device tensors [N], the form power_on_device takes them in."""
     torch = _torch()
+    return tuple(torch.as_tensor(np.ascontiguousarray(a), device=device) for a in (tau, w, data))
+
+
+def power_on_device(lib, series, model, n_series, grid, float_mean, device):
+    """rvm_gls_power on the current stream: (power [F][S], freq [F]) device tensors.  series: upload_series's
+    (tau, w, data); model: None or a contiguous device tensor [N][S]."""
+    torch = _torch()
+    tau, w, data = series
     f0, df, F = grid
     N, S = int(tau.numel()), int(n_series)
     power = torch.empty((F, S), dtype=torch.float64, device=device)
     freq = torch.empty(F, dtype=torch.float64, device=device)
-    ws = torch.empty(max(lib.rvm_gls_workspace_bytes(N, F, S) // 8, 2), dtype=torch.float64, device=device)
+    ws = _lib.workspace(lib.rvm_gls_workspace_bytes(N, F, S), torch.float64, device, floor=2)
     _lib.check(lib.rvm_gls_power(tau.data_ptr(), w.data_ptr(), N, data.data_ptr(), ptr(model), S, S, f0, df, 0, F,
                                  1 if float_mean else 0, power.data_ptr(), S, freq.data_ptr(), ws.data_ptr(),
                                  _lib.stream_handle()), "rvm_gls_power")
@@ -140,7 +147,6 @@ def gls(obs, grid=None, float_mean=True, device=None):
     device = torch.device("cuda" if device is None else device)
     lib = _lib.load()
     with torch.cuda.device(device):
-        dev = [torch.as_tensor(np.ascontiguousarray(a), device=device) for a in (tau, w, rv)]
-        power, freq = power_on_device(lib, dev[0], dev[1], dev[2], None, 1, grid, float_mean, device)
+        power, freq = power_on_device(lib, upload_series(tau, w, rv, device), None, 1, grid, float_mean, device)
         power, freq = power[:, 0].cpu().numpy(), freq.cpu().numpy()
     return Periodogram(freq=freq, power=power, period_days=period_days(freq))

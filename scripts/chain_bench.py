@@ -19,22 +19,12 @@ Prints ONE JSON line and writes it to --out (profiles/chain_diag_bench.json).  F
 asserted.
 """
 import argparse
-import json
 import os
 import statistics
-import sys
 import time
 
 import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(ROOT, "rvel-mcmc_amd"), os.path.join(ROOT, "oracle")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-S2_PLANETS = [{"m": 1.2e-3, "a": 0.88, "h": 0.218, "k": 0.015, "l": 0.3},
-              {"m": 2.1e-3, "a": 1.44 + 0.11, "h": 0.16, "k": 0.02, "l": 2.2}]
-S2_SCALES = {"m": 1.5e-3, "a": 0.3, "h": 0.1, "k": 0.1, "l": np.pi / 2.}
+from side_bench import ROOT, emit, steady_ensemble, subset_recorder, timed
 
 
 def parse():
@@ -55,34 +45,9 @@ def main():
 
     from rvmcmc import driver
     from rvmcmc.chain import ChainRecorder
-    from rvmcmc.ensemble import EnsembleSampler
-    from rvmcmc.observations import FakeObservation
-    from rvmcmc.state import State
 
-    torch.cuda.set_device(0)
-    state = State(planets=[dict(p) for p in S2_PLANETS])
-    np.random.seed(2017)
-    obs = FakeObservation(state, Npoints=100, error=1.5e-4, errorVar=2.5e-5, tmax=120.)
-    scales = np.array([S2_SCALES[k] for k in state.get_rawkeys()])
+    _, _, ens = steady_ensemble(args, "chain_bench")
     W = args.walkers
-    X0 = state.get_params()[None] + 0.1e-2 * scales * np.random.normal(size=(W, state.Nvars))
-    ens = EnsembleSampler(W, state, obs, seed=2017)
-    ens.set_positions(X0)
-    ens.compute_lnprob()
-    t_prog = time.perf_counter()
-    for i in range(args.burn_in):
-        ens.step()
-        if i % 64 == 0 and time.perf_counter() - t_prog > 20.0:
-            t_prog = time.perf_counter()
-            print(f"chain_bench: burn-in iteration {i}", file=sys.stderr, flush=True)
-    ens.check_faults()
-
-    def timed(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        return time.perf_counter() - t0
 
     # ---- (i) the bare loop against run_mcmc with a recorder, alternating ------------------------------
     rec = ChainRecorder(ens, capacity=(args.rounds + 1) * args.steps)
@@ -95,8 +60,8 @@ def main():
     ens.run_mcmc(args.steps, rec)  # (warm: both paths once, the recorder's kernel loaded)
     bare_ms, rec_ms = [], []
     for _ in range(args.rounds):
-        bare_ms.append(1e3 * timed(bare) / args.steps)
-        rec_ms.append(1e3 * timed(lambda: ens.run_mcmc(args.steps, rec)) / args.steps)
+        bare_ms.append(1e3 * timed(bare)[0] / args.steps)
+        rec_ms.append(1e3 * timed(lambda: ens.run_mcmc(args.steps, rec))[0] / args.steps)
     b, r = statistics.median(bare_ms), statistics.median(rec_ms)
     record = {"steps_per_window": args.steps, "rounds": args.rounds, "walkers_recorded": rec.n_walkers,
               "bytes_per_iteration": 8 * rec.n_walkers * (rec.n_params + 1),
@@ -107,11 +72,10 @@ def main():
     torch.cuda.empty_cache()
 
     # ---- (ii) diagnostics() against the copy to the host and driver.ess --------------------------------
-    stride = max(1, ens.nloc // 512)  # bench.py's recorded subset
-    rec = ChainRecorder(ens, capacity=args.chain_steps, walker_stride=stride, lnprob=False)
-    t_run = timed(lambda: ens.run_mcmc(args.chain_steps, rec))
+    rec = subset_recorder(ens, args.chain_steps)
+    t_run = timed(lambda: ens.run_mcmc(args.chain_steps, rec))[0]
     ens.check_faults()
-    first = timed(lambda: rec.diagnostics())
+    first = timed(lambda: rec.diagnostics())[0]
     diag_s = []
     for _ in range(args.repeat):
         t0 = time.perf_counter()
@@ -124,7 +88,7 @@ def main():
     t0 = time.perf_counter()
     _, taus = driver.ess(c)
     t_fft = time.perf_counter() - t0
-    diag = {"chain_steps": rec.n, "walkers_recorded": rec.n_walkers, "walker_stride": stride,
+    diag = {"chain_steps": rec.n, "walkers_recorded": rec.n_walkers, "walker_stride": rec.walker_stride,
             "run_mcmc_ms_per_iteration": 1e3 * t_run / args.chain_steps,
             "diagnostics_first_call_s": first, "diagnostics_s": statistics.median(diag_s), "diagnostics_s_all": diag_s,
             "host_copy_s": t_copy, "host_driver_ess_s": t_fft, "host_total_s": t_copy + t_fft,
@@ -136,10 +100,7 @@ def main():
             "ess_min_recorded_walkers": float(np.min(d.ess))}
     result = {"metric": "chain recording overhead and diagnostics time (2-planet, 100 obs, 4096 walkers, steady state)",
               "walkers": W, "burn_in": args.burn_in, "record": record, "diagnostics": diag}
-    line = json.dumps(result)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
-    print(line)
+    emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -13,12 +13,20 @@ state and its synthetic observations (tests/conftest.py), on one stream:
 
     ens_fused / ens_spec / ens_three / ens_injected   EnsembleSampler, W = 64, 4 iterations: fused half-steps,
                       speculative iterations, the three-launch path with Philox and with injected draws
-    rec               ChainRecorder(thin=2) over ens_fused: chain, tau, quantiles
+    rec               ChainRecorder(thin=2) over ens_fused: chain, tau, quantiles; predict() and
+                      residual_periodogram() over 64 drawn states, every field
     pt                PTSampler(3, 32, adapt=True, swap_every=1): 4 iterations, freeze, record, 2 more
     mh_fused / mh_unfused                             MhChains, 64 chains, 4 steps
     smala_<hessian>_<fused|separate>, smala_fixed_*   SmalaChains, 32 chains, 3 steps; fixed: resolve_tol = 0
     ck_ens / ck_pt / ck_mh / ck_smala                 2 steps, checkpoint (kept beside the .npz), 2 more; with
                       --restore DIR the first two steps are replaced by restoring DIR's checkpoint
+
+and the read-outs on synthetic, fixed-seed inputs at the edges of the pieces they share:
+
+    ro_chain          a chain [70][3][300]: moments, autocovariance over lag_blocks(70), summary(), draw(33)
+    ro_quantiles      rvm_rows_quantiles through both load paths, an all-NaN row among the rows
+    ro_gls            rvm_gls_power at N = 5 and 6, F = 65, S = 129, float_mean on and off, a NaN model column
+    ro_ladder         rvm_pt_ladder_update at T = 3, W = 260 with the moments
 """
 import argparse
 import dataclasses
@@ -33,8 +41,8 @@ sys.path.append(os.path.join(ROOT, "rvel-mcmc_amd"))  # (after PYTHONPATH: anoth
 import torch  # noqa: E402
 from conftest import S2_PLANETS, S2_SCALES, s2_obs_oracle  # noqa: E402
 
-from rvmcmc import engine  # noqa: E402
-from rvmcmc.chain import ChainRecorder  # noqa: E402
+from rvmcmc import _lib, engine, periodogram  # noqa: E402
+from rvmcmc.chain import ChainRecorder, _rows_quantiles, lag_blocks  # noqa: E402
 from rvmcmc.ensemble import EnsembleSampler  # noqa: E402
 from rvmcmc.mcmc import MhChains  # noqa: E402
 from rvmcmc.smala import SmalaChains  # noqa: E402
@@ -82,7 +90,109 @@ def ensemble(mode, obs, record=False):
     out = _ens_out(e)
     if record:
         out = dict(chain=rec.chain().cpu().numpy(), tau=rec.diagnostics().tau, quantiles=rec.summary().quantiles)
+        t = engine.obs_arrays(obs)[0]
+        out.update(_fields("predict_", rec.predict(np.linspace(t.min(), t.max(), 37), n_samples=64, seed=2,
+                                                   return_samples=True)))
+        out.update(_fields("residual_", rec.residual_periodogram(n_samples=64, seed=2, return_samples=True)))
     return out
+
+
+def _fields(prefix, result):
+    """Every field of a result dataclass as a host array (device tensors copied)."""
+    d = {prefix + f.name: getattr(result, f.name) for f in dataclasses.fields(result)}
+    return {k: v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v) for k, v in d.items() if v is not None}
+
+
+Q7 = (0.0, 0.025, 0.16, 0.5, 0.84, 0.975, 1.0)
+
+
+def _f64(a, device="cuda"):
+    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=device)
+
+
+def ro_chain():
+    """A synthetic chain [70][3][300]: two walker blocks of 256 with a partial one, the lags 0 .. 69 over tiles of 16
+    with a partial one, an odd parameter count over the covariance's tiles of 2."""
+    class Held:  # what a ChainRecorder asks of a sampler: a device and a segment's shape
+        device = torch.device("cuda", torch.cuda.current_device())
+
+        def _chain_segments(self):
+            return [dict(x=torch.zeros((3, 300), dtype=torch.float64, device=self.device), n=300)]
+
+    rec = ChainRecorder(Held(), capacity=70, lnprob=False)
+    x = np.cumsum(np.random.default_rng(11).standard_normal((70, 3, 300)), 0)  # (random walks: the lags correlate)
+    rec._chain.copy_(_f64(x * np.array([1.0, 1e-3, 40.0])[:, None] + np.array([0.5, -2.0, 1e3])[:, None]))
+    rec.n = 70
+    mean, m2 = (v.clone() for v in rec._moments(0, 70, 0))
+    acov = np.concatenate([rec.autocov(0, 70, lo, hi - lo, mean).cpu().numpy() for lo, hi in lag_blocks(70)], 1)
+    X, idx = rec.draw(33, discard=5, seed=9, draw_id=2)
+    out = dict(mean=mean.cpu().numpy(), m2=m2.cpu().numpy(), acov=acov, draw_X=X.cpu().numpy(),
+               draw_idx=idx.cpu().numpy())
+    out.update(_fields("summary_", rec.summary(discard=5, q=Q7)))
+    # the quantiles on the chain in place: 16-byte aligned, even strides -- the wide loads
+    P, W = rec.n_params, rec.n_walkers
+    qa, na = _rows_quantiles(rec.lib, rec._chain.data_ptr(), P, W, 70, P * W, W, np.array(Q7), rec.device)
+    out.update(chain_quantiles=qa.cpu().numpy(), chain_n_valid=na.cpu().numpy())
+    return out
+
+
+def ro_quantiles():
+    """rvm_rows_quantiles over [4][2500] (two segments of 2048, the second partial; row 1 all NaN, row 3 partly):
+    16-byte aligned with an even stride, and the same values one double further on with an odd stride."""
+    rng = np.random.default_rng(12)
+    data = rng.standard_normal((4, 2500)) * np.array([1.0, 1.0, 1e-300, 1e5])[:, None]
+    data[1], data[3, ::7], data[0, :3] = np.nan, np.nan, (np.inf, -np.inf, -0.0)
+    wide = _f64(data)
+    buf = torch.empty(1 + 4 * 2501, dtype=torch.float64, device="cuda")
+    narrow = buf[1:].view(4, 2501)[:, :2500]
+    narrow.copy_(wide)
+    assert wide.data_ptr() % 16 == 0 and narrow.data_ptr() % 16 == 8 and narrow.stride(0) % 2 == 1
+    out, lib = {}, _lib.load()
+    for name, x in (("wide", wide), ("narrow", narrow)):
+        qv, nv = _rows_quantiles(lib, x.data_ptr(), 4, x.stride(0), 1, x.stride(0), 2500, np.array(Q7), x.device)
+        out.update({name + "_quantiles": qv.cpu().numpy(), name + "_n_valid": nv.cpu().numpy()})
+    return out
+
+
+def ro_gls():
+    """rvm_gls_power at N = 5 and 6 (a table row padded to even, and not), F = 65 and S = 129 (one past the product
+    kernel's tile of 64 x 128), with and without the floating mean, one model column all NaN."""
+    lib, out = _lib.load(), {}
+    sh = torch.cuda.current_stream().cuda_stream
+    for N in (5, 6):
+        rng = np.random.default_rng(13 + N)
+        t, sigma = np.sort(rng.uniform(0.0, 30.0, N)), rng.uniform(0.5, 1.5, N)
+        data, model = rng.standard_normal(N), 0.3 * rng.standard_normal((N, 129))
+        model[:, 17] = np.nan
+        for fm in (1, 0):
+            tau, w = periodogram.series_inputs(t, sigma, bool(fm))
+            d = [_f64(a) for a in (tau, w, data, model)]
+            power, freq = torch.empty((65, 129), dtype=torch.float64, device="cuda"), _f64(np.zeros(65))
+            ws = torch.empty(max(lib.rvm_gls_workspace_bytes(N, 65, 129) // 8, 2), dtype=torch.float64, device="cuda")
+            _lib.check(lib.rvm_gls_power(d[0].data_ptr(), d[1].data_ptr(), N, d[2].data_ptr(), d[3].data_ptr(), 129,
+                                         129, 0.01, 0.003, 2, 65, fm, power.data_ptr(), 129, freq.data_ptr(),
+                                         ws.data_ptr(), sh), "rvm_gls_power")
+            out.update({f"power_N{N}_fm{fm}": power.cpu().numpy(), f"freq_N{N}_fm{fm}": freq.cpu().numpy()})
+    return out
+
+
+def ro_ladder():
+    """rvm_pt_ladder_update twice at T = 3, Wh = 130 (W = 260: the strided partials run past one block of 256),
+    the moments on."""
+    lib, rng, T, Wh = _lib.load(), np.random.default_rng(14), 3, 130
+    i64 = dict(dtype=torch.int64, device="cuda")
+    swapped = torch.as_tensor(rng.integers(0, 50, (T - 1, 2 * Wh)).astype(np.int32), device="cuda")
+    lnp = [_f64(-50.0 + 5.0 * rng.standard_normal(T * Wh)) for _ in range(2)]
+    betas, ratios, moments = _f64([1.0, 0.4, 0.05]), _f64(np.zeros(T - 1)), _f64(np.zeros((T, 2)))
+    prev, refused, ws = torch.zeros(T - 1, **i64), torch.zeros(1, **i64), torch.empty(3 * T - 1, **i64)
+    for _ in range(2):
+        _lib.check(lib.rvm_pt_ladder_update(T, Wh, swapped.data_ptr(), lnp[0].data_ptr(), lnp[1].data_ptr(), 0.05,
+                                            betas.data_ptr(), prev.data_ptr(), ratios.data_ptr(), refused.data_ptr(),
+                                            moments.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                   "rvm_pt_ladder_update")
+        swapped += torch.as_tensor(rng.integers(0, 3, (T - 1, 2 * Wh)).astype(np.int32), device="cuda")
+    return {k: v.cpu().numpy() for k, v in dict(betas=betas, ratios=ratios, moments=moments, totals_prev=prev,
+                                                refused=refused).items()}
 
 
 def _pt_out(p):
@@ -173,6 +283,7 @@ def dump(out_dir, restore):
     for name, build, out_of in (("ck_ens", lambda: _ck_ens(obs), _ens_out), ("ck_pt", lambda: _pt(obs), _pt_out),
                                 ("ck_mh", lambda: _mh(obs), _mh_out), ("ck_smala", lambda: _smala(obs), _smala_out)):
         cases[name] = lambda a=(name, build, out_of): checkpointed(*a, out_dir, restore)
+    cases.update(ro_chain=ro_chain, ro_quantiles=ro_quantiles, ro_gls=ro_gls, ro_ladder=ro_ladder)
     for name, run in cases.items():
         np.savez(os.path.join(out_dir, name + ".npz"), **run())
         torch.cuda.synchronize()

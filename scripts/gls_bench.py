@@ -25,22 +25,13 @@ bench.py records.  On that chain, for periodogram.freq_grid's default grid and o
 Prints ONE JSON line and writes it to --out (profiles/gls_bench.json).  Figures are recorded, not asserted.
 """
 import argparse
-import json
 import os
 import statistics
 import sys
-import time
 
 import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(ROOT, "rvel-mcmc_amd"), os.path.join(ROOT, "oracle")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-S2_PLANETS = [{"m": 1.2e-3, "a": 0.88, "h": 0.218, "k": 0.015, "l": 0.3},
-              {"m": 2.1e-3, "a": 1.44 + 0.11, "h": 0.16, "k": 0.02, "l": 2.2}]
-S2_SCALES = {"m": 1.5e-3, "a": 0.3, "h": 0.1, "k": 0.1, "l": np.pi / 2.}
+import side_bench
+from side_bench import ROOT, emit, steady_recorder
 PEAK_FP64_TFLOPS = 78.6  # MI355X vector FP64 (its matrix FP64 rate is the same)
 
 
@@ -63,65 +54,20 @@ def main():
     from scipy.signal import lombscargle
 
     from rvmcmc import _lib, engine, periodogram
-    from rvmcmc.chain import ChainRecorder
-    from rvmcmc.ensemble import EnsembleSampler
-    from rvmcmc.observations import FakeObservation
-    from rvmcmc.state import State
 
-    torch.cuda.set_device(0)
-    state = State(planets=[dict(p) for p in S2_PLANETS])
-    np.random.seed(2017)
-    obs = FakeObservation(state, Npoints=100, error=1.5e-4, errorVar=2.5e-5, tmax=120.)
-    scales = np.array([S2_SCALES[k] for k in state.get_rawkeys()])
+    _, obs, _, rec = steady_recorder(args, "gls_bench")
     W = args.walkers
-    X0 = state.get_params()[None] + 0.1e-2 * scales * np.random.normal(size=(W, state.Nvars))
-    ens = EnsembleSampler(W, state, obs, seed=2017)
-    ens.set_positions(X0)
-    ens.compute_lnprob()
-    t_prog = time.perf_counter()
-    for i in range(args.burn_in):
-        ens.step()
-        if i % 64 == 0 and time.perf_counter() - t_prog > 20.0:
-            t_prog = time.perf_counter()
-            print(f"gls_bench: burn-in iteration {i}", file=sys.stderr, flush=True)
-    ens.check_faults()
-    stride = max(1, ens.nloc // 512)  # bench.py's recorded subset
-    rec = ChainRecorder(ens, capacity=args.chain_steps, walker_stride=stride, lnprob=False)
-    ens.run_mcmc(args.chain_steps, rec)
-    ens.check_faults()
-    torch.cuda.synchronize()
-    print("gls_bench: chain recorded", file=sys.stderr, flush=True)
 
     lib = _lib.load()
     t, rvobs, er = engine.obs_arrays(obs)
     tau, w = periodogram.series_inputs(t, er)
     N, S = len(t), args.samples
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-
-    def timed(fn):
-        torch.cuda.synchronize()
-        a = time.perf_counter()
-        r = fn()
-        torch.cuda.synchronize()
-        return time.perf_counter() - a, r
 
     def repeat(fn):
-        first, r = timed(fn)
-        rest = []
-        for _ in range(args.repeat):
-            dt, r = timed(fn)
-            rest.append(dt)
-        return first, rest, r
+        return side_bench.repeat(fn, args.repeat)
 
     def events(fn):
-        out = []
-        for _ in range(args.repeat + 1):
-            ev[0].record()
-            fn()
-            ev[1].record()
-            torch.cuda.synchronize()
-            out.append(ev[0].elapsed_time(ev[1]) * 1e-3)
-        return out[1:]
+        return side_bench.events(fn, args.repeat)
 
     f0, df, F0 = periodogram.freq_grid(t)
     grids = {"default": (f0, df, F0), f"finer_x{args.finer}": (df / args.finer, df / args.finer, F0 * args.finer)}
@@ -143,7 +89,7 @@ def main():
         h_first, host_s, hb = repeat(host)
 
         # ---- the launches alone ----
-        dev = [torch.as_tensor(np.ascontiguousarray(a), device=rec.device) for a in (tau, w, rvobs)]
+        dev = periodogram.upload_series(tau, w, rvobs, rec.device)
         model = pb.rv.contiguous()
         sh = torch.cuda.current_stream().cuda_stream
         f64 = dict(dtype=torch.float64, device=rec.device)
@@ -188,7 +134,7 @@ def main():
     SL, grid = args.large_samples, grids[f"finer_x{args.finer}"]
     F = grid[2]
     f64 = dict(dtype=torch.float64, device=rec.device)
-    dev = [torch.as_tensor(np.ascontiguousarray(a), device=rec.device) for a in (tau, w, rvobs)]
+    dev = periodogram.upload_series(tau, w, rvobs, rec.device)
     gen = torch.Generator(device=rec.device).manual_seed(1)
     model = dev[2][:, None] + 1e-4 * torch.randn((N, SL), generator=gen, **f64)
     power, ws = torch.empty((F, SL), **f64), torch.empty(lib.rvm_gls_workspace_bytes(N, F, SL) // 8, **f64)
@@ -212,10 +158,7 @@ def main():
     print("gls_bench: large product done", file=sys.stderr, flush=True)
     result = {"metric": "residual periodogram on the device against the host route (2-planet, 100 obs, 4096 walkers)",
               "walkers": W, "burn_in": args.burn_in, "chain_steps": rec.n, "grids": out, "product_large": large}
-    line = json.dumps(result)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
-    print(line)
+    emit(result, args.out)
 
 
 if __name__ == "__main__":

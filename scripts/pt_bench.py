@@ -29,15 +29,8 @@ import sys
 import time
 
 import numpy as np
+from side_bench import ROOT, ball, burn_in, emit, s2_problem
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(ROOT, "rvel-mcmc_amd"), os.path.join(ROOT, "oracle")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-S2_PLANETS = [{"m": 1.2e-3, "a": 0.88, "h": 0.218, "k": 0.015, "l": 0.3},
-              {"m": 2.1e-3, "a": 1.44 + 0.11, "h": 0.16, "k": 0.02, "l": 2.2}]
-S2_SCALES = {"m": 1.5e-3, "a": 0.3, "h": 0.1, "k": 0.1, "l": np.pi / 2.}
 COUNTERS = ("refined", "unresolved", "nonfinite", "handoff_timeouts")
 
 
@@ -67,25 +60,19 @@ def run_part(args):
     import torch
 
     from rvmcmc.ensemble import EnsembleSampler
-    from rvmcmc.observations import FakeObservation
-    from rvmcmc.state import State
     from rvmcmc.tempering import PTSampler
 
-    torch.cuda.set_device(0)
-    state = State(planets=[dict(p) for p in S2_PLANETS])
-    np.random.seed(2017)
-    obs = FakeObservation(state, Npoints=100, error=1.5e-4, errorVar=2.5e-5, tmax=120.)
-    scales = np.array([S2_SCALES[k] for k in state.get_rawkeys()])
+    state, obs, scales = s2_problem()
     if args.part == "pt":
         T, W = args.ntemps, args.walkers
-        X0 = state.get_params()[None, None] + 0.1e-2 * scales * np.random.normal(size=(T, W, state.Nvars))
+        X0 = ball(state, scales, T, W)
         smp = PTSampler(T, W, state, obs, seed=2017, swap_every=args.swap_every, adapt=args.adapt,
                         adaptation_lag=args.adaptation_lag, adaptation_time=args.adaptation_time)
         betas_start = [float(b) for b in smp.betas]
         nwalk = T * W
     else:
         T, W = 1, args.ensemble_walkers
-        X0 = state.get_params()[None] + 0.1e-2 * scales * np.random.normal(size=(W, state.Nvars))
+        X0 = ball(state, scales, W)
         smp = EnsembleSampler(W, state, obs, seed=2017)
         smp.fused = False
         nwalk = W
@@ -94,12 +81,8 @@ def run_part(args):
     smp.fault_check_every = 0
     smp.set_positions(X0)
     smp.compute_lnprob()
-    t_prog = t_burn = time.perf_counter()
-    for i in range(args.burn_in):
-        smp.step()
-        if i % 64 == 0 and time.perf_counter() - t_prog > 20.0:
-            t_prog = time.perf_counter()
-            print(f"pt_bench[{args.part}]: burn-in iteration {i}", file=sys.stderr, flush=True)
+    t_burn = time.perf_counter()
+    burn_in(smp, args.burn_in, f"pt_bench[{args.part}]")
     if args.part == "pt" and args.adapt:
         smp.freeze_ladder()  # the warmup and the timed iterations run on the adapted, fixed ladder
     for _ in range(args.warmup):
@@ -173,11 +156,9 @@ def main():
         result["fixed_ladder"] = {k: fixed[k] for k in ("betas", "swap_fraction", "ms_per_iteration", "evals_per_s")}
         result["min_swap_fraction"] = min(result["pt"]["swap_fraction"])
         result["fixed_ladder_min_swap_fraction"] = min(fixed["swap_fraction"])
-        with open(args.out, "w") as f:
-            f.write(json.dumps(result) + "\n")
     else:
         result["pt_over_ensemble"] = result["pt"]["evals_per_s"] / result["ensemble"]["evals_per_s"]
-    print(json.dumps(result))
+    emit(result, args.out if args.adapt else None)
 
 
 if __name__ == "__main__":

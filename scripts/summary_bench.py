@@ -21,22 +21,14 @@ Prints ONE JSON line and writes it to --out (profiles/summary_bench.json).  Figu
 asserted.
 """
 import argparse
-import json
 import os
 import statistics
 import sys
 import time
 
 import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(ROOT, "rvel-mcmc_amd"), os.path.join(ROOT, "oracle")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-S2_PLANETS = [{"m": 1.2e-3, "a": 0.88, "h": 0.218, "k": 0.015, "l": 0.3},
-              {"m": 2.1e-3, "a": 1.44 + 0.11, "h": 0.16, "k": 0.02, "l": 2.2}]
-S2_SCALES = {"m": 1.5e-3, "a": 0.3, "h": 0.1, "k": 0.1, "l": np.pi / 2.}
+import side_bench
+from side_bench import ROOT, emit, steady_recorder, timed
 SELECT_PASSES = 8  # rvm_summary.hip: 8-bit digits of a 64-bit key
 
 
@@ -57,52 +49,18 @@ def main():
     args = parse()
     import torch
 
-    from rvmcmc import chain as chain_mod
-    from rvmcmc.chain import ChainRecorder
-    from rvmcmc.ensemble import EnsembleSampler
-    from rvmcmc.observations import FakeObservation
-    from rvmcmc.state import State
+    from rvmcmc import _lib, chain as chain_mod
 
-    torch.cuda.set_device(0)
-    state = State(planets=[dict(p) for p in S2_PLANETS])
-    np.random.seed(2017)
-    obs = FakeObservation(state, Npoints=100, error=1.5e-4, errorVar=2.5e-5, tmax=120.)
-    scales = np.array([S2_SCALES[k] for k in state.get_rawkeys()])
+    state, obs, ens, rec = steady_recorder(args, "summary_bench")
     W = args.walkers
-    X0 = state.get_params()[None] + 0.1e-2 * scales * np.random.normal(size=(W, state.Nvars))
-    ens = EnsembleSampler(W, state, obs, seed=2017)
-    ens.set_positions(X0)
-    ens.compute_lnprob()
-    t_prog = time.perf_counter()
-    for i in range(args.burn_in):
-        ens.step()
-        if i % 64 == 0 and time.perf_counter() - t_prog > 20.0:
-            t_prog = time.perf_counter()
-            print(f"summary_bench: burn-in iteration {i}", file=sys.stderr, flush=True)
-    ens.check_faults()
-    stride = max(1, ens.nloc // 512)  # bench.py's recorded subset
-    rec = ChainRecorder(ens, capacity=args.chain_steps, walker_stride=stride, lnprob=False)
-    ens.run_mcmc(args.chain_steps, rec)
-    ens.check_faults()
-    torch.cuda.synchronize()
-    print("summary_bench: chain recorded", file=sys.stderr, flush=True)
     n, P, Wr, t0 = rec.n - args.discard, rec.n_params, rec.n_walkers, args.discard
     q = np.array(chain_mod.DEFAULT_Q)
 
-    def timed(fn):
-        torch.cuda.synchronize()
-        a = time.perf_counter()
-        r = fn()
-        torch.cuda.synchronize()
-        return time.perf_counter() - a, r
-
     def repeat(fn):
-        first, r = timed(fn)
-        rest = []
-        for _ in range(args.repeat):
-            dt, r = timed(fn)
-            rest.append(dt)
-        return first, rest, r
+        return side_bench.repeat(fn, args.repeat)
+
+    def events(fn):
+        return side_bench.events(fn, args.repeat)
 
     # ---- (i) summary() against to_numpy() + np.quantile + np.cov ------------------------------------------
     first, dev_s, sm = repeat(lambda: rec.summary(discard=t0))
@@ -154,18 +112,6 @@ def main():
 
     # ---- (iii) the select alone, and a copy of the same bytes ----------------------------------------------
     x = rec.chain()[t0:]
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-
-    def events(fn):
-        out = []
-        for _ in range(args.repeat + 1):
-            ev[0].record()
-            fn()
-            ev[1].record()
-            torch.cuda.synchronize()
-            out.append(ev[0].elapsed_time(ev[1]) * 1e-3)
-        return out[1:]
-
     sel_s = events(lambda: chain_mod._rows_quantiles(rec.lib, x.data_ptr(), P, Wr, n, P * Wr, Wr, q, rec.device))
     dst = torch.empty_like(x)
     copy_s = events(lambda: dst.copy_(x))
@@ -174,7 +120,7 @@ def main():
     mom_s = events(lambda: rec._moments(t0, rec.n, 0))
     center = rec._mean[0].mean(1).contiguous()
     cov = torch.empty((P, P), dtype=torch.float64, device=rec.device)
-    ws = torch.empty(max(rec.lib.rvm_chain_cov_workspace_bytes(P, Wr) // 8, 1), dtype=torch.float64, device=rec.device)
+    ws = _lib.workspace(rec.lib.rvm_chain_cov_workspace_bytes(P, Wr), torch.float64, rec.device)
     cov_s = events(lambda: rec.lib.rvm_chain_cov(rec.chain().data_ptr(), P, Wr, t0, rec.n, center.data_ptr(),
                                                  cov.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream))
     summary["device_moments_s"] = statistics.median(mom_s)
@@ -188,10 +134,7 @@ def main():
     result = {"metric": "posterior summaries on the device against the host route (2-planet, 100 obs, 4096 walkers)",
               "walkers": W, "burn_in": args.burn_in, "chain_steps": rec.n, "discard": t0, "summary": summary,
               "predict": predict, "select": select}
-    line = json.dumps(result)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
-    print(line)
+    emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -3,7 +3,8 @@ GPU): over a grid of plans and launch sizes the dynamic-LDS request is LoglLds's
 the layouts' comments state, every range of it lies inside without overlap, and the choice keeps its
 invariants; and the layout of every shape the GPU tests name (tests/test_gpu_logl.py, and the adaptive plans of
 tests/test_gpu_resolve_systems.py) is pinned, each value derived from the rule.  rvm_plan_host.cpp is built with the host compiler and a small driver, as
-tests/test_hedge_wait_host_cpu.py does."""
+tests/test_hedge_wait_host_cpu.py does.  The same driver reaches rvm_internal.h's blocks_of and RVM_QNAN, which the
+sampler and read-out launchers share: the block count at the edges of a block and of int32, the NaN's bits."""
 import pytest
 
 from support import host_driver_report
@@ -12,6 +13,7 @@ DRIVER = r"""
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 #include "rvm_plan_host.h"
 using namespace rvm;
@@ -126,7 +128,16 @@ int main() {
         std::printf(", \"%s%d:%d\": [%d, %d, %d, %d, %d, %d, %d, %u, %u, %u]", apins[i][1] ? "i" : "p", apins[i][0],
                     apins[i][2], Y.G, Y.cx, Y.nA, Y.nB, Y.tB, Y.splitA, Y.lsx, Y.grid_x, Y.grid_y, Y.block);
     }
-    std::printf("}}\n");
+    // the launchers' block count (rvm_internal.h blocks_of) at the edges of a block of 256 and at the largest count
+    // the ABI admits, where n + 255 does not fit an int32; and the read-outs' quiet NaN, bit for bit
+    std::printf("}, \"blocks_of\": [");
+    const long long ns[6] = {0, 1, 255, 256, 257, INT32_MAX};
+    for (int i = 0; i < 6; i++) std::printf("%s%u", i ? ", " : "", blocks_of((uint64_t)ns[i], 256));
+    std::printf(", %u, %u]", blocks_of((uint64_t)2 * INT32_MAX, 256), blocks_of((uint64_t)INT32_MAX, 2));
+    const double qnan = RVM_QNAN;
+    unsigned long long bits;
+    std::memcpy(&bits, &qnan, sizeof bits);
+    std::printf(", \"qnan_bits\": \"%016llx\"}\n", bits);
     return 0;
 }
 """
@@ -229,3 +240,10 @@ PINS.update({
 @pytest.mark.parametrize("shape", sorted(PINS))
 def test_layout_of_the_gpu_tests_shapes(report, shape):
     assert report["pins"][shape] == PINS[shape]
+
+
+def test_block_count_and_quiet_nan(report):
+    # ceil(n / 256) for n = 0, 1, 255, 256, 257, INT32_MAX (2^23 blocks: n + 255 computed in int32 would wrap),
+    # then rvm_stretch_iteration_end's 2 n threads at n = INT32_MAX and rvm_chain_cov's tiles of 2 parameters
+    assert report["blocks_of"] == [0, 1, 1, 1, 2, 1 << 23, 1 << 24, 1 << 30]
+    assert report["qnan_bits"] == "7ff8000000000000"
