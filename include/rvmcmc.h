@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define RVM_ABI_VERSION 13
+#define RVM_ABI_VERSION 14
 
 /* per-walker status codes (status_out) */
 #define RVM_STATUS_OK 0
@@ -71,6 +71,8 @@ extern "C" {
                                    slot whose partner's first-half decision (already final) rules it
                                    out, not refined by the adaptive resolution; rvm_stretch_iteration_end
                                    never reads it.  logl -inf                                          */
+#define RVM_STATUS_ESCAPE 6     /* rvm_stability_advance's status only: a planet's Jacobi |r| beyond
+                                   r_max at a block end                                                */
 
 #define RVM_MAX_PLANETS 4
 #define RVM_MAX_LEVELS 6
@@ -626,6 +628,57 @@ int rvm_gls_power(const double* tau, const double* w, int32_t n_obs, const doubl
                   int64_t model_ld, int32_t n_series, double f0, double df, int64_t k0, int32_t n_freq,
                   int32_t float_mean, double* power_out, int64_t power_ld, double* freq_out, void* workspace,
                   void* stream);
+
+/* ---- dynamical stability of states already in device memory ----------------------------------------
+ * Which states of a posterior survive: n states integrated with the likelihood kernel's Wisdom-Holman
+ * map over 10^4 .. 10^6 orbits, far beyond the observations' span, with the running extremes of each
+ * planet's osculating Jacobi elements.  No plan: there is no observation schedule.  The conventions of the
+ * summary entry points hold: device pointers, no allocation, no synchronisation, stream-ordered and
+ * capturable, no floating-point atomics, the same bits from run to run; argument errors return < 0
+ * before any HIP call and name the argument in rvm_last_error.
+ *
+ *   n >= 1 states, NP = n_planets (1 .. RVM_MAX_PLANETS), R = 5 NP, or 7 NP when inclined (0 or 1).
+ *   params [R][n]     kernel rows, as rvm_logl_batch takes them; read by both calls, never written
+ *   xv [6][NP][n]     Jacobi rx ry rz vx vy vz of each planet (rz = vz = 0 for planar states)
+ *   ext [3][NP][n]    a_min, a_max, e2_max: the running extremes of the osculating Jacobi elements
+ *   status int32 [n]  the state's status code
+ *   steps int64 [n]   Wisdom-Holman steps completed when the state ended, or so far
+ *   hill_factor >= 0, the same in both calls.  h > 0 and finite, sample_every >= 1, n_blocks >= 1; r_max <= 0
+ *   (or NaN) turns the escape test off.  n_alive_out int64 [1], nullable.
+ *
+ * Elements of planet p from its Jacobi (r, v), GM the interior mass M_p of its coordinate (1 + m_1 + .. + m_p),
+ * every operation one IEEE double operation, fma where written:
+ *   r2 = fma(rz, rz, fma(ry, ry, rx rx));  |r| = sqrt(r2);  ir = 1 / |r|;
+ *   v2 = fma(vz, vz, fma(vy, vy, vx vx));  beta = fma(2 GM, ir, -v2);  a = GM / beta;
+ *   hx = fma(ry, vz, -(rz vy)), hy = fma(rz, vx, -(rx vz)), hz = fma(rx, vy, -(ry vx));
+ *   h2 = fma(hz, hz, fma(hy, hy, hx hx));  e2 = fma(-(h2 beta), 1 / (GM GM), 1).
+ * An unbound orbit is not a status: it shows as a_min <= 0 or e2_max >= 1.
+ *
+ * stability_init: the likelihood kernel's setup at t = 0 (prior, Pal -> heliocentric -> Jacobi, the Hill exit
+ * distance and its check on every pair before the first step).  status = RVM_STATUS_PRIOR or
+ * RVM_STATUS_ENCOUNTER exactly as that setup gives them, else RVM_STATUS_OK; xv = the state at t = 0;
+ * a_min = a_max = a and e2_max = e2 of it; steps = 0.  A state that is not OK gets NaN in xv and ext.
+ *
+ * stability_advance: every state whose status is RVM_STATUS_OK runs n_blocks blocks; any other is not
+ * written, bit for bit.  A block starts from xv alone -- |r| and 1 / |r| as above, the interaction evaluated
+ * at those positions (with its pair test) -- and is sample_every steps of size h of the likelihood kernel's
+ * map, K(h/2) [D K]^(sample_every - 1) D K(h/2), with the 8-term Stumpff series and the gated drift.  At its
+ * end steps += sample_every, and in this order:
+ *   1. a pair came within the exit distance at any kick of the block: RVM_STATUS_ENCOUNTER; xv, ext stay as
+ *      at the previous block end;
+ *   2. |r|, a or e2 of some planet is not finite: RVM_STATUS_NONFINITE; xv, ext stay likewise;
+ *   3. a_min = fmin(a_min, a), a_max = fmax(a_max, a), e2_max = fmax(e2_max, e2); xv = the state;
+ *   4. |r| > r_max for some planet: RVM_STATUS_ESCAPE.
+ * A state that has ended runs no further block.  Since a block starts from xv alone and the lane constants
+ * are rebuilt from params as stability_init built them, the result does not depend on how the blocks are
+ * split over calls: n_blocks = a + b equals n_blocks = a, then b, bit for bit; nor on the state's column or
+ * its neighbours.  n_alive_out receives the number of states still RVM_STATUS_OK (a second launch, an
+ * integer count). */
+int rvm_stability_init(int32_t n_planets, int32_t inclined, int32_t n, const double* params, double hill_factor,
+                       double* xv, double* ext, int32_t* status, int64_t* steps, void* stream);
+int rvm_stability_advance(int32_t n_planets, int32_t inclined, int32_t n, const double* params, double hill_factor,
+                          double h, int32_t sample_every, int32_t n_blocks, double r_max, double* xv, double* ext,
+                          int32_t* status, int64_t* steps, int64_t* n_alive_out, void* stream);
 
 const char* rvm_last_error(void);
 int rvm_abi_version(void);

@@ -299,6 +299,23 @@ int main() {
     expect(rvm_pt_ladder_update(1, 4, nullptr, nullptr, nullptr, 0.5, nullptr, nullptr, nullptr, nullptr, nullptr,
                                 nullptr, nullptr) == 0,
            "pt ladder of one temperature");
+    // the stability screen: every refusal before any HIP call
+    {
+        int64_t s1 = 0;
+        expect(rvm_stability_init(0, 0, 4, &d1, 1.0, &d1, &d1, &i1, &s1, nullptr) < 0, "stability n_planets 0");
+        expect(rvm_stability_init(2, 0, 0, &d1, 1.0, &d1, &d1, &i1, &s1, nullptr) < 0, "stability n 0");
+        expect(rvm_stability_init(2, 0, 4, nullptr, 1.0, &d1, &d1, &i1, &s1, nullptr) < 0, "stability null params");
+        expect(rvm_stability_advance(2, 0, 4, &d1, 1.0, 0.0, 4, 1, 0.0, &d1, &d1, &i1, &s1, nullptr, nullptr) < 0,
+               "stability h 0");
+        expect(rvm_stability_advance(2, 0, 4, &d1, 1.0, NAN, 4, 1, 0.0, &d1, &d1, &i1, &s1, nullptr, nullptr) < 0,
+               "stability h nan");
+        expect(rvm_stability_advance(2, 1, 4, &d1, 1.0, 0.3, 0, 1, 0.0, &d1, &d1, &i1, &s1, nullptr, nullptr) < 0,
+               "stability sample_every 0");
+        expect(rvm_stability_advance(2, 1, 4, &d1, 1.0, 0.3, 4, 0, 0.0, &d1, &d1, &i1, &s1, nullptr, nullptr) < 0,
+               "stability n_blocks 0");
+        expect(rvm_stability_advance(2, 1, 4, &d1, 1.0, 0.3, 4, 1, 0.0, &d1, &d1, nullptr, &s1, nullptr, nullptr) < 0,
+               "stability null status");
+    }
     // the recorded chain: refusals before any HIP call, the column and lag bounds in 64-bit arithmetic
     expect(rvm_chain_record(2, 4, &d1, 16, 0, INT64_MAX, &d1, 8, 0, nullptr, nullptr, nullptr) < 0,
            "chain record stride overflow");

@@ -515,6 +515,48 @@ int rvm_gls_power(const double* tau, const double* w, int32_t n_obs, const doubl
                                          (hipStream_t)stream));
 }
 
+// ---- dynamical stability (rvm_stability.hip) ----
+// the shape both entry points share: the refusal's text, or null
+static const char* stability_bad_shape(int32_t n_planets, int32_t inclined, int32_t n) {
+    if (n_planets < 1 || n_planets > RVM_MAX_PLANETS) return "n_planets must be 1 .. 4";
+    if (inclined != 0 && inclined != 1) return "inclined must be 0 or 1";
+    if (n < 1) return "n must be >= 1";
+    return nullptr;
+}
+
+int rvm_stability_init(int32_t n_planets, int32_t inclined, int32_t n, const double* params, double hill_factor,
+                       double* xv, double* ext, int32_t* status, int64_t* steps, void* stream) {
+    const Entry at{"rvm_stability_init"};
+    if (const char* m = stability_bad_shape(n_planets, inclined, n)) return at.bad(m);
+    if (!params) return at.null("params");
+    if (const char* m = bad_hill(hill_factor)) return at.bad(m);
+    if (!xv) return at.null("xv");
+    if (!ext) return at.null("ext");
+    if (!status) return at.null("status");
+    if (!steps) return at.null("steps");
+    return at.done(rvm::launch_stability_init(n_planets, inclined, n, params, hill_factor, xv, ext, status, steps,
+                                              (hipStream_t)stream));
+}
+
+int rvm_stability_advance(int32_t n_planets, int32_t inclined, int32_t n, const double* params, double hill_factor,
+                          double h, int32_t sample_every, int32_t n_blocks, double r_max, double* xv, double* ext,
+                          int32_t* status, int64_t* steps, int64_t* n_alive_out, void* stream) {
+    const Entry at{"rvm_stability_advance"};
+    if (const char* m = stability_bad_shape(n_planets, inclined, n)) return at.bad(m);
+    if (!params) return at.null("params");
+    if (const char* m = bad_hill(hill_factor)) return at.bad(m);
+    if (!(h > 0.0) || !std::isfinite(h)) return at.bad("h must be > 0 and finite");
+    if (sample_every < 1) return at.bad("sample_every must be >= 1");
+    if (n_blocks < 1) return at.bad("n_blocks must be >= 1");
+    if (!xv) return at.null("xv");
+    if (!ext) return at.null("ext");
+    if (!status) return at.null("status");
+    if (!steps) return at.null("steps");
+    return at.done(rvm::launch_stability_advance(n_planets, inclined, n, params, hill_factor, h, sample_every,
+                                                 n_blocks, r_max, xv, ext, status, steps, n_alive_out,
+                                                 (hipStream_t)stream));
+}
+
 int rvm_mh_propose(int32_t n_params, int32_t n_chains, int64_t chain_begin, const double* x, const double* scales,
                    double step_size, uint64_t seed, uint64_t iteration, const double* draws, double* q_out,
                    void* stream) {

@@ -92,6 +92,11 @@ hipError_t launch_gls_basis(const double* tau, int N, int64_t ld, double f0, dou
 hipError_t launch_gls_power(const double* tau, const double* w, int N, const double* data, const double* model,
                             int64_t model_ld, int S, double f0, double df, int64_t k0, int F, int float_mean,
                             double* power, int64_t power_ld, double* freq_out, double* ws, hipStream_t st);
+hipError_t launch_stability_init(int NP, int inclined, int n, const double* params, double hill_factor, double* xv,
+                                 double* ext, int32_t* status, int64_t* steps, hipStream_t st);
+hipError_t launch_stability_advance(int NP, int inclined, int n, const double* params, double hill_factor, double h,
+                                    int sample_every, int n_blocks, double r_max, double* xv, double* ext,
+                                    int32_t* status, int64_t* steps, int64_t* n_alive, hipStream_t st);
 hipError_t launch_fd_params(int P, int n, const double* x, double rel, const double* fl, double* out, hipStream_t st);
 hipError_t launch_smala_derive(int P, int C, int E, const double* x, double rel, const double* fl,
                                const double* lp_st, const int32_t* st_st, const double* rv, const double* w,

@@ -18,12 +18,13 @@ RVM_STATUS_ENCOUNTER = 2
 RVM_STATUS_NONFINITE = 3
 RVM_STATUS_UNRESOLVED = 4
 RVM_STATUS_SKIPPED = 5  # rvm_stretch_iteration_begin status_spec only
+RVM_STATUS_ESCAPE = 6  # rvm_stability_advance only
 RVM_MAX_PLANETS = 4
 RVM_MAX_LEVELS = 6
 RVM_MAX_EPOCHS_PER_DIRECTION = 1700  # epochs with t >= 0, and with t < 0, per plan
 RVM_MAX_QUANTILES = 16  # rvm_rows_quantiles
 RVM_N_COUNTERS = 7  # rvm_plan_counters
-ABI_VERSION = 13  # include/rvmcmc.h RVM_ABI_VERSION
+ABI_VERSION = 14  # include/rvmcmc.h RVM_ABI_VERSION
 
 
 class RvmConfig(C.Structure):
@@ -151,6 +152,9 @@ SIGNATURES = {
     "rvm_gls_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rvm_gls_power": (C.c_int, [_dp, _dp, C.c_int32, _dp, _dp, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                 C.c_int64, C.c_int32, C.c_int32, _dp, C.c_int64, _dp, _dp, _dp]),
+    "rvm_stability_init": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]),
+    "rvm_stability_advance": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, C.c_double, C.c_double, C.c_int32,
+                                        C.c_int32, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp]),
     "rvm_fd_params": (C.c_int, [C.c_int32, C.c_int32, _dp, C.c_double, _dp, _dp, _dp]),
     "rvm_logl_derivs_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rvm_logl_derivs": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int32, C.POINTER(C.c_int32), C.c_double, _dp, _dp,

@@ -460,6 +460,21 @@ class ChainRecorder:
         out = periodogram.PeriodogramBands(freq=freq, q=q, bands=bands, n_valid=n_valid, data_power=data_power)
         return dataclasses.replace(out, power=power, **kept) if return_samples else out
 
+    def stability(self, n_samples=1024, discard=0, seed=0, samples=None, **screen_kwargs):
+        """stability.StabilityResult of n_samples states drawn from the recorded steps [discard, n) (or of the
+        caller's samples [P][S]): which of the posterior's states survive an integration far beyond the
+        observations' span (stability.screen: years / orbits, steps_per_orbit, sample_every, r_max,
+        chunk_steps, return_samples).  The sampler's state, parameter map and Hill factor as in predict(); idx
+        [S], the drawn states' indices into chain() (None with the caller's samples), restricts a summary to
+        the stable subset.  Synchronises after every launch of chunk_steps steps."""
+        from . import stability
+
+        state, _ = self._evaluator(False, "state / pmap: nothing to integrate the states with")
+        X, idx = (samples, None) if samples is not None else self.draw(n_samples, discard, seed)
+        screen_kwargs.setdefault("hill_factor", getattr(self.sampler, "hill_factor", state.hillRadiusFactor))
+        screen_kwargs.setdefault("pmap", self.sampler.pmap)
+        return dataclasses.replace(stability.screen(state, X, **screen_kwargs), idx=idx)
+
 
 def run_mcmc(sampler, n_steps, recorder=None):
     """n_steps iterations of sampler.step(), with recorder.observe() after each: every thin-th one is
